@@ -29,6 +29,14 @@ Parallelism: ``dpN`` (default) runs one engine replica per GPU, like the referen
 per-GPU work is fixed, so scaling is weak.  ``--tp N`` runs one tensor-parallel
 engine over N GPUs (RCCL/xGMI all-reduce) per replica instead.
 Weights are random-init bf16 of the real architecture (no checkpoints offline).
+
+A plain run does only what the result line needs: start the service, warm up, time the
+waves, print the line.  Prompts, weights and the sampling seed of every request are fixed
+by the arguments.  ``--dump-outputs DIR`` writes, as ``.npy``, each request's first
+generated token in the last timed wave (prefill and first-token sampling only) and, with
+``--mode engine``, all of its tokens: ``dump_outputs`` says how far each repeats from run
+to run.  ``--full`` adds the measurements that take runs of their own (at N > 1 the RCCL /
+xGMI all-reduce probe after the timed waves).
 """
 from __future__ import annotations
 
@@ -39,11 +47,21 @@ import statistics
 import sys
 import time
 
-import torch
-import torch.distributed as dist
-
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
+
+# torch takes seconds to import: service mode launches its API server first and imports
+# it while the server starts (the bench process needs it for the model's vocabulary
+# size and, at N > 1, for the gloo group only)
+torch = dist = None
+
+
+def _import_torch() -> None:
+    global torch, dist
+    import torch as _torch
+    import torch.distributed as _dist
+    torch, dist = _torch, _dist
+
 
 BASELINE_METRIC = "output tokens/sec + p50 TTFT, Llama-3-8B K8s service at 1/2/4/8 MI355X"
 _METRIC_NAMES = {"llama-3-8b": "Llama-3-8B", "llama-3-70b": "Llama-3-70B",
@@ -94,9 +112,19 @@ def parse():
     ap.add_argument("--api-server-count", type=int, default=0,
                     help="service mode: API processes per engine (0: server default)")
     ap.add_argument("--startup-timeout", type=float, default=1800)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: at N > 1 in service "
+                         "mode the RCCL / xGMI all-reduce probe after the timed waves "
+                         "(benchmarks/comm_probe.py).  A plain run sets up, warms up, times "
+                         "the waves and prints the result line")
     ap.add_argument("--no-comm-probe", dest="comm_probe", action="store_false", default=True,
-                    help="service mode, N > 1: skip the RCCL / xGMI all-reduce probe that runs "
-                         "after the timed waves (benchmarks/comm_probe.py)")
+                    help="--full, service mode, N > 1: skip the all-reduce probe all the same")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed waves, write what the last one returned to its "
+                         "caller, as far as it repeats from run to run, as DIR/<name>.npy "
+                         "(float32, prompt order): first_token_ids [num_prompts], and with "
+                         "--mode engine output_token_ids [num_prompts, output_len]; N > 1: "
+                         "one set per replica, <name>_rank<R>.npy")
     ap.add_argument("--router-workers", type=int, default=0,
                     help="service mode: router processes in front of all replicas "
                          "(0: one per replica, at most 16)")
@@ -126,16 +154,24 @@ def _k9m_top() -> dict:
     return {f"{n}x{k}:{kind}": list(v) for (m, n, k, kind), v in sorted(plan.items()) if m == mx}
 
 
+def _request_seeds(n: int, base: int) -> list:
+    """One sampling seed per request of a wave, fixed by the wave and its position in it:
+    without one the engine derives the seed from the order in which the requests reach
+    it, which differs from run to run over HTTP."""
+    return [(base * 65536 + i) & 0x7FFFFFFF for i in range(n)]
+
+
 def run_wave(engine, args, wave: int, rank: int):
     from kubernetes_gpu_cluster_amd.engine.sequence import SamplingParams
     g = torch.Generator().manual_seed(1000 * wave + rank)
     vocab = engine.mcfg.vocab_size
-    sp = SamplingParams(temperature=args.temperature, top_p=1.0, max_tokens=args.output_len,
-                        ignore_eos=True)
+    seeds = _request_seeds(args.num_prompts, 1000 * wave + rank)
     t0 = time.monotonic()
     seqs = []
     for i in range(args.num_prompts):
         ids = torch.randint(100, vocab - 100, (args.input_len,), generator=g).tolist()
+        sp = SamplingParams(temperature=args.temperature, top_p=1.0, max_tokens=args.output_len,
+                            ignore_eos=True, seed=seeds[i])
         seqs.append(engine.add_request(ids, sp, request_id=f"w{wave}-r{rank}-{i}", arrival_time=t0))
     steps = 0
     while engine.has_unfinished():
@@ -146,11 +182,52 @@ def run_wave(engine, args, wave: int, rank: int):
     ttfts = [s.first_token_time - s.arrival_time for s in seqs]
     tpots = [(s.last_token_time - s.first_token_time) / max(1, len(s.output_token_ids) - 1)
              for s in seqs]
-    return out_toks, t1 - t0, ttfts, tpots, steps
+    return out_toks, t1 - t0, ttfts, tpots, steps, [list(s.output_token_ids) for s in seqs]
+
+
+def dump_outputs(args, rank: int, world: int, token_ids: list, whole_rows: bool) -> None:
+    """--dump-outputs, from the last timed wave's generated token ids (one list per request,
+    in prompt order; float32 holds every id of a vocabulary below 2**24 exactly):
+
+    ``first_token_ids`` [num_prompts], both modes: prefill and first-token sampling only.
+    The first token comes from the prompt's prefill and the request's own sampling seed,
+    both fixed by the arguments, and from how the service batched that prefill: which
+    prompts shared a step, and where a prompt was split over two, follows the order of
+    arrival and sets the rows (and with them the kernel) of the prefill and lm_head
+    GEMMs.  It is the least noisy column, not an exact one: of the pairs of service runs
+    of one build compared on MI355X most were identical, and one differed in about one id
+    of 256.  A single differing id is therefore no sign of a changed build; compare
+    decode, and anything that must be exact, with ``--mode engine``.  -1: the request
+    returned no token, or in service
+    mode no text (the server withholds a trailing incomplete byte sequence, so a stream of
+    a few tokens that its busy frontend detokenizes in one piece can come back empty; not
+    one of ``output_len`` 256, whose first event leaves long before its last token).
+
+    ``output_token_ids`` [num_prompts, output_len], -1 padded, ``--mode engine`` only: there
+    every request is added before the first step, so the batches a sequence is computed in
+    are the same in every run.  The service batches requests as they arrive, and the batch
+    size of a decode step selects its GEMM kernels, so a sequence's later logits differ in
+    their last bf16 bits with the company it had; one differently sampled token then
+    changes all that follow.  Measured on MI355X, two service runs of one build agreed on
+    98.4% of the second tokens, and after 256 tokens on 231 of 256 whole rows in one pair
+    of runs and on none in another: written out, the later tokens would compare arrival
+    times, not builds.  Two engine-mode runs were identical in all 256 x 256 positions."""
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    first = np.array([row[0] if row else -1 for row in token_ids], dtype=np.float32)
+    np.save(os.path.join(args.dump_outputs, f"first_token_ids{sfx}.npy"), first)
+    if whole_rows:
+        ids = np.full((len(token_ids), args.output_len), -1.0, dtype=np.float32)
+        for i, row in enumerate(token_ids):
+            row = row[:args.output_len]
+            ids[i, :len(row)] = row
+        np.save(os.path.join(args.dump_outputs, f"output_token_ids{sfx}.npy"), ids)
 
 
 def main_engine(args):
     import logging
+    _import_torch()
     logging.basicConfig(level=getattr(logging, args.log_level.upper(), logging.WARNING),
                         format="%(asctime)s %(name)s %(levelname)s %(message)s")
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -211,9 +288,10 @@ def main_engine(args):
     barrier() if tp == 1 else None
     t0 = time.monotonic()
     toks, ttfts, tpots, steps, wall = 0, [], [], 0, 0.0
+    last_ids = []
     if is_driver:
         for wv in range(args.steps):
-            o, dt, tt, tp_, st = run_wave(engine, args, wv, rank)
+            o, dt, tt, tp_, st, last_ids = run_wave(engine, args, wv, rank)
             toks += o
             ttfts += tt
             tpots += tp_
@@ -228,6 +306,8 @@ def main_engine(args):
     host_t = engine.host_timing() if is_driver and hasattr(engine, "host_timing") else None
     if is_driver:
         engine.shutdown()
+        if args.dump_outputs:
+            dump_outputs(args, rank, world, last_ids, whole_rows=True)
     # aggregate over replicas (drivers) -- every rank participates in the collectives
     if world > 1:
         t = torch.tensor([elapsed if is_driver else 0.0, float(toks), float(steps)],
@@ -359,6 +439,31 @@ def _engine_args(args, cpu: bool) -> list:
     return ea
 
 
+def _streamed_ids(lines: list) -> list:
+    """Token ids of one streamed completion from its whole text (all events joined, so the
+    server's chunking of the stream cannot matter): the synthetic tokenizer of a model
+    served without checkpoint files writes an id outside its byte range as ``<id>`` and
+    one inside it as that byte (utils/tokenizer.py), so the text maps back to ids.  The
+    completions API returns text only, and what the text does not tell stays untold: a
+    byte id that is no valid UTF-8 arrives as U+FFFD and is written as -2, and a sampled
+    BOS / EOS id is not in the text at all (the next id takes its place).  Of Llama-3's
+    128256 ids, 258 are of these kinds."""
+    import re
+    from kubernetes_gpu_cluster_amd.utils.tokenizer import SyntheticTokenizer
+    off = SyntheticTokenizer.OFF
+
+    def byte_ids(s: str) -> list:
+        return [i for ch in s for i in ([-2] if ch == "\ufffd" else
+                                        [b + off for b in ch.encode("utf-8")])]
+    text = "".join(json.loads(raw[5:])["choices"][0].get("text") or "" for raw in lines)
+    ids, pos = [], 0
+    for m in re.finditer(r"<(\d+)>", text):
+        ids += byte_ids(text[pos:m.start()])
+        ids.append(int(m.group(1)))
+        pos = m.end()
+    return ids + byte_ids(text[pos:])
+
+
 def main_service(args):
     """One replica per ``tp`` ranks: the leading rank launches API server + router and
     drives its own client; every rank joins the barriers and the aggregation (gloo,
@@ -366,7 +471,6 @@ def main_service(args):
     import asyncio
     import urllib.request
     from kubernetes_gpu_cluster_amd.benchmarks import serving_client as sc
-    from kubernetes_gpu_cluster_amd.models.configs import resolve_model
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -379,8 +483,8 @@ def main_service(args):
     leader = rank % tp == 0
     if world > 1:
         import datetime
+        _import_torch()
         dist.init_process_group("gloo", timeout=datetime.timedelta(seconds=args.startup_timeout + 600))
-    vocab = resolve_model(args.model)[0].vocab_size
     procs, logs = [], []
     api_url = url = None
     res_all, windows, eng = [], [], {}
@@ -395,7 +499,12 @@ def main_service(args):
                                              _server_devices(local_rank, tp, cpu),
                                              _engine_args(args, cpu)))
             _note(f"rank {rank}: API server {api_url} (tp {tp}); waiting for health")
-            asyncio.run(sc.wait_healthy([api_url], args.startup_timeout, procs, _note))
+        # (imports torch: after the launch, so that it overlaps the server's start-up)
+        from kubernetes_gpu_cluster_amd.models.configs import resolve_model
+        vocab = resolve_model(args.model)[0].vocab_size
+        if leader:
+            asyncio.run(sc.wait_healthy([api_url], args.startup_timeout, procs, _note,
+                                        interval=0.2))
         # ONE service endpoint for the whole job, as the reference deploys DP:
         # replicaCount engine pods behind one vllm-router-service
         # (/root/reference/values-01-minimal-example2.yaml:10,23-49).  Rank 0 runs the
@@ -414,7 +523,8 @@ def main_service(args):
             procs.append(router)
             _note(f"router {url}: {workers} worker process(es) over {len(backends)} "
                   f"replica(s); waiting for health")
-            asyncio.run(sc.wait_healthy([url], args.startup_timeout, procs, _note))
+            asyncio.run(sc.wait_healthy([url], args.startup_timeout, procs, _note,
+                                        interval=0.2))
             _note("service is up")
         if world > 1:
             box = [url]
@@ -434,9 +544,10 @@ def main_service(args):
             timed = make_prompts(args.steps, 0) if leader else []
             out = []
             async with sc.new_session() as s:
-                for prompts in warm:
-                    r, _, _ = await sc.run_wave(s, url, args.model, prompts, args.output_len,
-                                                temperature=args.temperature)
+                for w, prompts in enumerate(warm):
+                    r, _, _ = await sc.run_wave(
+                        s, url, args.model, prompts, args.output_len, temperature=args.temperature,
+                        seeds=_request_seeds(len(prompts), 7_000_000 + 1000 * w + rank))
                     bad = [x for x in r if not x.ok]
                     if bad:
                         raise RuntimeError(f"warmup: {len(bad)} requests failed "
@@ -451,9 +562,14 @@ def main_service(args):
                     t_lo = max(ents)
                 t0 = time.monotonic()
                 c0 = sc.cpu_seconds(router.pid) if router is not None else 0.0
-                for prompts in timed:
-                    out.append(await sc.run_wave(s, url, args.model, prompts, args.output_len,
-                                                 temperature=args.temperature))
+                for w, prompts in enumerate(timed):
+                    # --dump-outputs keeps the last wave's stream lines as they arrive
+                    # (a list append per event); they are parsed after the timed region
+                    r, _, _ = await sc.run_wave(
+                        s, url, args.model, prompts, args.output_len, temperature=args.temperature,
+                        seeds=_request_seeds(len(prompts), 1000 * w + rank),
+                        keep=bool(args.dump_outputs) and w == len(timed) - 1)
+                    out.append(r)
                 if world > 1:
                     dist.barrier()
                 t1 = time.monotonic()
@@ -461,8 +577,11 @@ def main_service(args):
                 return out, t0, t1 - t0, c1 - c0, t_lo
 
         waves_out, t0, elapsed, router_cpu, t_lo = asyncio.run(run_all())
-        for r, lo, hi in waves_out:
+        for r in waves_out:
             res_all += r
+        if leader and args.dump_outputs and waves_out:
+            dump_outputs(args, rank, world, [_streamed_ids(r.lines or []) for r in waves_out[-1]],
+                         whole_rows=False)
         # one window over all timed waves: behind the shared router a replica also serves
         # other ranks' requests, whose waves need not line up with this rank's
         windows.append((min(t_lo, t0), t0 + elapsed))
@@ -478,7 +597,7 @@ def main_service(args):
     probe = None
     devs = [d for d in os.environ.get("KGC_BENCH_DEVICES", "").split(",") if d]
     shared = len(devs) > len(set(devs))
-    if world > 1 and not cpu and args.comm_probe and not shared:
+    if args.full and world > 1 and not cpu and args.comm_probe and not shared:
         # (replicas sharing one GPU: RCCL takes one rank per device, so no probe)
         probe = _comm_probe(rank, world, local_rank)
     ok = [r for r in res_all if r.ok]
@@ -525,7 +644,7 @@ def main_service(args):
             # router CPU-seconds per wall second over the timed waves (all its workers)
             "router_cpu_util": round(router_cpu / elapsed, 3) if elapsed > 0 else None,
             "router_workers": args.router_workers or max(1, min(16, replicas)),
-            # after the timed waves, outside the timed region: RCCL all-reduce bus
+            # --full, after the timed waves, outside the timed region: RCCL all-reduce bus
             # bandwidth and the xGMI kernel vs RCCL on this node's GPUs (N > 1)
             "comm_probe": probe,
             "config": {"model": args.model, "global_batch": args.num_prompts * replicas,

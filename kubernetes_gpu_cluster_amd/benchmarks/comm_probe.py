@@ -2,7 +2,7 @@
 all-reduce kernel (parallel/custom_allreduce.py) against RCCL at the decode message
 sizes, measured on the machine the job runs on.
 
-``bench.py --gpus N`` (N > 1) runs it once per rank after the timed waves, in a child
+``bench.py --full --gpus N`` (N > 1) runs it once per rank after the timed waves, in a child
 process per GPU with a hard time limit, and reports rank 0's table in its JSON line
 ("comm_probe"), so the driver's 1/2/4/8-GPU scaling runs also record what RCCL and the
 xGMI kernel do at that world size.  The one-shot / two-shot / RCCL hand-over points

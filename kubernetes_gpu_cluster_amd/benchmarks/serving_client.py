@@ -48,17 +48,25 @@ class Result:
     e2e: float = 0.0
     tokens: int = 0
     itl: list = field(default_factory=list)
+    lines: Optional[list] = None    # the stream's raw SSE data lines (``keep`` only)
 
 
 async def one_request(session: aiohttp.ClientSession, url: str, model: str, prompt,
-                      out_len: int, temperature: float = 1.0) -> Result:
+                      out_len: int, temperature: float = 1.0, seed: Optional[int] = None,
+                      keep: bool = False) -> Result:
     """One streamed completion.  Tokens are counted from what arrived: the
     ``stream_options.include_usage`` event (completion_tokens) that the server sends
     before ``[DONE]``.  A stream cut short (no usage event or no [DONE]) is a failed
-    request that credits no tokens -- never ``max_tokens`` on faith."""
+    request that credits no tokens -- never ``max_tokens`` on faith.
+    ``seed``: the request's sampling seed (None: the engine derives one from the order of
+    arrival).  ``keep``: the raw data lines of the choices stay in ``Result.lines``, to be
+    parsed after a timed region."""
     body = {"model": model, "prompt": prompt, "max_tokens": out_len, "ignore_eos": True,
             "stream": True, "temperature": temperature,
             "stream_options": {"include_usage": True}}
+    if seed is not None:
+        body["seed"] = seed
+    lines = [] if keep else None
     t0 = time.monotonic()
     ttft, last, itl = None, t0, []
     ntok, done = None, False
@@ -84,19 +92,25 @@ async def one_request(session: aiohttp.ClientSession, url: str, model: str, prom
             else:
                 itl.append(now - last)
             last = now
+            if keep:
+                lines.append(raw)
     ok = ttft is not None and done and ntok is not None
-    return Result(ok, 200, ttft, last - t0, ntok if ok else 0, itl)
+    return Result(ok, 200, ttft, last - t0, ntok if ok else 0, itl, lines)
 
 
 async def run_wave(session, url: str, model: str, prompts, out_len: int,
                    request_rate: float = float("inf"), seed: int = 0,
-                   temperature: float = 1.0) -> tuple[list[Result], float, float]:
-    """-> (results, wave start, wave end) with host ``time.monotonic()`` stamps."""
+                   temperature: float = 1.0, seeds: Optional[list] = None,
+                   keep: bool = False) -> tuple[list[Result], float, float]:
+    """-> (results, wave start, wave end) with host ``time.monotonic()`` stamps.
+    ``seeds``: one sampling seed per prompt; ``keep``: see ``one_request``."""
     rng = random.Random(seed)
     t0 = time.monotonic()
     tasks = []
-    for p in prompts:
-        tasks.append(asyncio.create_task(one_request(session, url, model, p, out_len, temperature)))
+    for i, p in enumerate(prompts):
+        tasks.append(asyncio.create_task(one_request(
+            session, url, model, p, out_len, temperature,
+            seed=None if seeds is None else seeds[i], keep=keep)))
         if request_rate != float("inf"):
             await asyncio.sleep(rng.expovariate(request_rate))
     res = await asyncio.gather(*tasks)
@@ -173,8 +187,10 @@ def start_router(port: int, backends: list[str], log=None, workers: int = 1) -> 
                             stderr=subprocess.STDOUT if log is not None else None)
 
 
-async def wait_healthy(urls: list[str], timeout_s: float, procs=(), progress=None) -> None:
-    """Poll ``/health`` until 200; fail early when a launched process exits."""
+async def wait_healthy(urls: list[str], timeout_s: float, procs=(), progress=None,
+                       interval: float = 1.0) -> None:
+    """Poll ``/health`` every ``interval`` s until 200; fail early when a launched process
+    exits."""
     deadline = time.monotonic() + timeout_s
     last_note = time.monotonic()
     async with aiohttp.ClientSession() as s:
@@ -195,7 +211,7 @@ async def wait_healthy(urls: list[str], timeout_s: float, procs=(), progress=Non
                 if progress is not None and time.monotonic() - last_note > 20:
                     progress(f"waiting for {u}/health ({time.monotonic() - deadline + timeout_s:.0f}s)")
                     last_note = time.monotonic()
-                await asyncio.sleep(1.0)
+                await asyncio.sleep(interval)
 
 
 def cpu_seconds(pid: int) -> float:

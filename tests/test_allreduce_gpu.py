@@ -305,7 +305,7 @@ def test_xgmi_world_emulation(world, gpu):
 
 
 def test_comm_probe_two_ranks_on_one_gpu(gpu, tmp_path):
-    """benchmarks/comm_probe.py (run by bench.py at N > 1 on the real node): two ranks on
+    """benchmarks/comm_probe.py (run by bench.py --full at N > 1 on the real node): two ranks on
     cuda:0 with gloo standing in for RCCL; the xGMI kernel rows must be correct and the
     table complete (one-shot, two-shot, library time per size, crossover)."""
     import json

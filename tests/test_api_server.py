@@ -1,6 +1,7 @@
 """OpenAI API server: schema, SSE streaming, stop strings, health/metrics/models
 (CPU engine with a tiny random model)."""
 import json
+import os
 
 import pytest
 from fastapi.testclient import TestClient
@@ -173,7 +174,7 @@ def test_n_choices_and_penalties(client):
     assert client.post("/v1/completions", json={"prompt": "x", "presence_penalty": 5}).status_code == 400
 
 
-def test_shared_core_serves_two_frontends(tmp_path):
+def test_shared_core_serves_two_frontends(request):
     """--api-server-count: one engine core, two attached frontends; each frontend gets
     exactly its own requests' outputs, and a detached frontend leaves the core running."""
     import asyncio
@@ -181,7 +182,17 @@ def test_shared_core_serves_two_frontends(tmp_path):
     from kubernetes_gpu_cluster_amd.engine.sequence import SamplingParams
     from kubernetes_gpu_cluster_amd.entrypoints.engine_core import EngineCoreClient, start_core
     cfg = _cfg()
-    addr, key = str(tmp_path / "core.sock"), b"k" * 32
+    # sun_path holds ~107 bytes and pytest's tmp_path (base temp + user + test name) can
+    # exceed that: keep the socket in a short directory of its own, as the server does
+    # (api_server.py: mkdtemp(prefix="kgc-core-")), falling back to /tmp for a deep TMPDIR
+    import shutil
+    import tempfile
+    sock_dir = tempfile.mkdtemp(prefix="kgc-core-")
+    if len(os.path.join(sock_dir, "core.sock").encode()) > 100:
+        shutil.rmtree(sock_dir, ignore_errors=True)
+        sock_dir = tempfile.mkdtemp(prefix="kgc-core-", dir="/tmp")
+    request.addfinalizer(lambda: shutil.rmtree(sock_dir, ignore_errors=True))
+    addr, key = os.path.join(sock_dir, "core.sock"), b"k" * 32
     core = start_core(cfg, addr, key, 2)
     a = EngineCoreClient(cfg, connect=(addr, key), core_proc=core)
     b = EngineCoreClient(cfg, connect=(addr, key))

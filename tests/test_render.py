@@ -11,7 +11,9 @@ from kubernetes_gpu_cluster_amd.k8s.render import ValuesError, render, to_yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OURS = sorted(glob.glob(os.path.join(ROOT, "deploy/values/*.yaml")))
-REF = sorted(glob.glob("/root/reference/values-01-minimal-example*.yaml"))
+# the reference deployment's own values files, stored as fixtures (settings only)
+REF = sorted(glob.glob(os.path.join(ROOT, "tests/golden/reference/values-01-minimal-example*.yaml")))
+assert len(REF) == 9, REF
 
 
 def _load(p):
