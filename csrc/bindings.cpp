@@ -1202,6 +1202,75 @@ void skinny_gemm(Tensor C, Tensor X, Tensor W, std::optional<Tensor> bias, int64
                           X.stride(0), C.stride(0), np, tp, sp, (int)nss, stream());
 }
 
+// K9q (gemm_w8.hip): C = (X . W8^T) * scale (+ bias), or silu(gate) * up over a merged weight
+void w8_gemm(Tensor C, Tensor X, Tensor W8, Tensor scale, std::optional<Tensor> bias, int64_t mt,
+             int64_t nt, int64_t nw, bool ntl, bool silu) {
+  check_gpu(X, "X");
+  check_same_dev(X, W8, "W8");
+  check_same_dev(X, C, "C");
+  check_same_dev(X, scale, "scale");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(X.device());
+  TORCH_CHECK(X.dim() == 2 && W8.dim() == 2 && C.dim() == 2, "kgc.w8_gemm: 2-D operands");
+  TORCH_CHECK(C.scalar_type() == X.scalar_type() &&
+              (X.scalar_type() == at::kBFloat16 || X.scalar_type() == at::kHalf),
+              "kgc.w8_gemm: bf16/f16 X and C of one dtype");
+  TORCH_CHECK(W8.scalar_type() == at::kFloat8_e4m3fn, "kgc.w8_gemm: W8 must be float8_e4m3fn");
+  TORCH_CHECK(mt == 1 || mt == 2 || mt == 4, "kgc.w8_gemm: mt in {1,2,4}");
+  TORCH_CHECK(nt == 1 || nt == 2, "kgc.w8_gemm: nt in {1,2}");
+  TORCH_CHECK(nw == 4 || nw == 8 || nw == 16, "kgc.w8_gemm: nw in {4,8,16}");
+  TORCH_CHECK(!(mt == 4 && nt == 2 && nw == 16), "kgc.w8_gemm: (mt, nt, nw) = (4, 2, 16) is not built");
+  const int64_t M = X.size(0), K = X.size(1), N = W8.size(0);
+  TORCH_CHECK(M >= 1 && M <= 16 * mt, "kgc.w8_gemm: M must be in [1, 16*mt]");
+  TORCH_CHECK(W8.size(1) == K && W8.is_contiguous(), "kgc.w8_gemm: W8 [N, K] contiguous");
+  TORCH_CHECK(N % (16 * nt) == 0, "kgc.w8_gemm: N % (16*nt) != 0");
+  TORCH_CHECK(K % (64 * nw) == 0, "kgc.w8_gemm: K % (64*nw) != 0");
+  TORCH_CHECK(X.stride(1) == 1 && X.stride(0) % 8 == 0 && X.stride(0) >= K,
+              "kgc.w8_gemm: X rows dense, 16B aligned");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == N,
+              "kgc.w8_gemm: scale fp32 [N]");
+  if (silu) {   // merged [gate; up] weight [2I, K] -> C [M, I]
+    TORCH_CHECK(nt == 2 && !bias.has_value() && N % 32 == 0,
+                "kgc.w8_gemm: silu epilogue needs nt=2, no bias, N % 32 == 0");
+    TORCH_CHECK(C.size(0) == M && C.size(1) == N / 2 && C.stride(1) == 1,
+                "kgc.w8_gemm: silu epilogue writes C [M, N/2]");
+  } else {
+    TORCH_CHECK(C.size(0) == M && C.size(1) == N && C.stride(1) == 1, "kgc.w8_gemm: C [M, N]");
+  }
+  TORCH_CHECK(N <= INT32_MAX && K <= INT32_MAX, "kgc.w8_gemm: dims overflow");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(X.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(W8.data_ptr()) % 16 == 0, "kgc.w8_gemm: alignment");
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N &&
+                bias->scalar_type() == X.scalar_type(), "kgc.w8_gemm: bias [N]");
+    check_same_dev(X, *bias, "bias");
+    bp = bias->data_ptr();
+  }
+  kgc::launch_w8_gemm(dt_code(X), (int)mt, (int)nt, (int)nw, ntl, silu, C.data_ptr(),
+                      X.data_ptr(), W8.data_ptr(), scale.data_ptr<float>(), bp, (int)M, (int)N,
+                      (int)K, X.stride(0), C.stride(0), stream());
+}
+
+// out[n, k] = round(W8[n, k] * scale[n]): a quantised weight widened for the library GEMM
+void w8_widen(Tensor out, Tensor W8, Tensor scale) {
+  check_gpu(W8, "W8");
+  check_same_dev(W8, out, "out");
+  check_same_dev(W8, scale, "scale");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(W8.device());
+  TORCH_CHECK(W8.dim() == 2 && W8.is_contiguous() && W8.scalar_type() == at::kFloat8_e4m3fn,
+              "kgc.w8_widen: W8 [N, K] float8_e4m3fn contiguous");
+  TORCH_CHECK(out.is_contiguous() && out.sizes() == W8.sizes() &&
+              (out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kHalf),
+              "kgc.w8_widen: out [N, K] bf16/f16 contiguous");
+  TORCH_CHECK(W8.size(1) % 16 == 0, "kgc.w8_widen: K % 16 != 0");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_contiguous() &&
+              scale.numel() == W8.size(0), "kgc.w8_widen: scale fp32 [N]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(W8.data_ptr()) % 16 == 0, "kgc.w8_widen: alignment");
+  kgc::launch_w8_widen(dt_code(out), out.data_ptr(), W8.data_ptr(), scale.data_ptr<float>(),
+                       W8.size(0), W8.size(1), stream());
+}
+
 void sample_stamps_enable(bool on) { kgc::sample_stamps_enable(on); }
 
 std::vector<int64_t> sample_stamps() {
@@ -1321,6 +1390,9 @@ TORCH_LIBRARY(kgc, m) {
   m.def("skinny_gemm(Tensor(a!) C, Tensor X, Tensor W, Tensor? bias, int mt, int nt, int nw, "
         "bool ntl, int epi=0, Tensor? gamma=None, float eps=1e-6, Tensor(b!)? norm_out=None, "
         "Tensor(c!)? ticket=None, Tensor(d!)? ssp=None, int nss=0) -> ()");
+  m.def("w8_gemm(Tensor(a!) C, Tensor X, Tensor W8, Tensor scale, Tensor? bias, int mt, int nt, "
+        "int nw, bool ntl, bool silu=False) -> ()");
+  m.def("w8_widen(Tensor(a!) out, Tensor W8, Tensor scale) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(kgc, CUDA, m) {
@@ -1358,4 +1430,6 @@ TORCH_LIBRARY_IMPL(kgc, CUDA, m) {
   m.impl("splitk_reduce_silu", &splitk_reduce_silu);
   m.impl("splitk_add_rms_norm", &splitk_add_rms_norm);
   m.impl("skinny_gemm", &skinny_gemm);
+  m.impl("w8_gemm", &w8_gemm);
+  m.impl("w8_widen", &w8_widen);
 }

@@ -109,6 +109,13 @@ void launch_skinny_gemm(int dtype, int mt, int nt, int nw, bool ntl, int epi, vo
                         float eps, int M, int N, int K, int64_t ldx, int64_t ldc, void* NO,
                         uint32_t* ticket, float* ssp, int nss, hipStream_t s);
 
+// K9q: weight-only FP8 skinny GEMM (gemm_w8.hip) and the e4m3 -> bf16/f16 weight widening.
+void launch_w8_gemm(int dtype, int mt, int nt, int nw, bool ntl, bool silu, void* C,
+                    const void* X, const void* W, const float* scale, const void* bias, int M,
+                    int N, int K, int64_t ldx, int64_t ldc, hipStream_t s);
+void launch_w8_widen(int dtype, void* out, const void* W, const float* scale, int64_t N,
+                     int64_t K, hipStream_t s);
+
 // K13/K14 MoE: routing, expert bucketing, grouped MFMA GEMM, weighted combine.
 int moe_block_n();
 int moe_block_k();

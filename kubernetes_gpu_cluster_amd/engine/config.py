@@ -21,6 +21,7 @@ _DTYPES = {"auto": None, "bfloat16": torch.bfloat16, "bf16": torch.bfloat16,
 
 
 KV_CACHE_DTYPES = ("auto", "bfloat16", "bf16", "float16", "fp16", "fp8", "fp8_e4m3")
+QUANTIZATION_METHODS = ("fp8",)
 
 
 @dataclasses.dataclass
@@ -45,6 +46,7 @@ class EngineConfig:
     disable_custom_all_reduce: bool = False
     trust_remote_code: bool = False
     kv_cache_dtype: str = "auto"
+    quantization: Optional[str] = None    # None | fp8 (weight-only W8A16, models/quant.py)
     seed: int = 0
     random_init: bool = False
     num_gpu_blocks_override: Optional[int] = None
@@ -138,6 +140,12 @@ def add_engine_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
     a("--trust-remote-code", action="store_true")
     a("--kv-cache-dtype", type=str, default="auto",
       help="auto (activation dtype) or fp8 / fp8_e4m3 (half the KV bytes)")
+    a("--quantization", "-q", type=str, default=None,
+      help="fp8: online weight-only FP8 (W8A16) of the dense Llama-family linears (qkv, o, "
+           "gate_up, down): half the weight bytes, so more KV blocks and a lighter weight "
+           "stream at decode batches <= 64 (K9q).  Larger batches and prefill widen each "
+           "weight back to the model dtype before the library GEMM, which moves MORE bytes "
+           "than unquantised weights would.  Not for MoE or OPT models")
     a("--seed", type=int, default=0)
     a("--random-init", action="store_true", help="random weights (offline benchmarking)")
     a("--load-format", type=str, default="auto", help="'dummy' == --random-init")
@@ -159,6 +167,9 @@ def config_from_args(ns: argparse.Namespace) -> EngineConfig:
     if ns.kv_cache_dtype not in KV_CACHE_DTYPES:
         raise ValueError(f"--kv-cache-dtype {ns.kv_cache_dtype} is not supported "
                          f"({'/'.join(KV_CACHE_DTYPES)})")
+    if ns.quantization is not None and ns.quantization not in QUANTIZATION_METHODS:
+        raise ValueError(f"--quantization {ns.quantization} is not supported "
+                         f"({'/'.join(QUANTIZATION_METHODS)})")
     return EngineConfig(
         model=ns.model, served_model_name=ns.served_model_name, tokenizer=ns.tokenizer,
         dtype=ns.dtype, tensor_parallel_size=ns.tensor_parallel_size,
@@ -170,7 +181,8 @@ def config_from_args(ns: argparse.Namespace) -> EngineConfig:
         prefill_first_max_gap_ms=ns.prefill_first_max_gap_ms,
         enable_prefix_caching=ns.enable_prefix_caching,
         disable_custom_all_reduce=ns.disable_custom_all_reduce,
-        trust_remote_code=ns.trust_remote_code, kv_cache_dtype=ns.kv_cache_dtype, seed=ns.seed,
+        trust_remote_code=ns.trust_remote_code, kv_cache_dtype=ns.kv_cache_dtype, quantization=ns.quantization,
+        seed=ns.seed,
         random_init=ns.random_init or ns.load_format == "dummy",
         num_gpu_blocks_override=ns.num_gpu_blocks_override, device=ns.device,
         moe_parallel=ns.moe_parallel, cuda_graph_max_bs=ns.cuda_graph_max_bs,

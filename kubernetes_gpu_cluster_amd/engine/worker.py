@@ -112,6 +112,9 @@ class Worker:
             if self.hb_store is not None and dist.get_rank() != getattr(self.ps, "global_base", 0):
                 self.heartbeat = Heartbeat(self.hb_store, dist.get_rank()).start()
         mcfg, _ = resolve_model(cfg.model)
+        if cfg.quantization is not None:
+            from ..models.quant import check_quantizable
+            check_quantizable(mcfg, cfg.quantization)      # MoE / OPT / unknown method: refuse
         self.dtype = cfg.torch_dtype(torch.bfloat16 if mcfg.arch != "opt" else torch.float16)
         if dev.type == "cpu" and self.dtype == torch.float16:
             self.dtype = torch.float32       # CPU oracle path
@@ -123,6 +126,11 @@ class Worker:
         self.mcfg, self.model = load_model(cfg.model, self.dtype, dev, cfg.random_init,
                                            seed=cfg.seed)
         _fault_perturb_shard(self.model, self.ps)
+        if cfg.quantization is not None:
+            # this rank's dense projection weights -> fp8 + row scales, before anything is
+            # packed or folded and before the KV pool is sized (models/quant.py)
+            from ..models.quant import quantize_model
+            quantize_model(self.model, cfg.quantization)
         if dev.type == "cuda" and not cfg.enforce_eager:
             # packed copies of the decode-GEMM weights for the K9m tiles, made before the
             # KV cache is sized so the pool accounts for them (ops/gemm.py)

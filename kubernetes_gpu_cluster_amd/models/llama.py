@@ -73,6 +73,7 @@ class LlamaAttention(nn.Module):
     def __init__(self, cfg: ModelConfig, layer_idx: int, dtype, device):
         super().__init__()
         self.cfg = cfg
+        self.dtype = dtype      # the activation dtype (a quantised qkv weight's is fp8)
         self.qkv_proj = QKVParallelLinear(cfg.hidden_size, cfg.head_dim, cfg.num_heads,
                                           cfg.num_kv_heads, bias=cfg.qkv_bias, dtype=dtype,
                                           device=device)
@@ -119,10 +120,10 @@ class LlamaAttention(nn.Module):
                 None if self.q_norm is None else self.q_norm.weight,
                 None if self.k_norm is None else self.k_norm.weight, self.cfg.rms_eps,
                 workspace=m.decode_workspace, grid_z=m.decode_grid_z, k_scale=ctx.k_scale,
-                v_scale=ctx.v_scale, dtype=self.qkv_proj.weight.dtype, row_scale=row_scale)
+                v_scale=ctx.v_scale, dtype=self.dtype, row_scale=row_scale)
             return o.view(o.shape[0], self.nq * self.cfg.head_dim)
         if row_scale is not None:
-            qkv = self._scaled_rows(qkv, row_scale, self.qkv_proj.weight.dtype)
+            qkv = self._scaled_rows(qkv, row_scale, self.dtype)
         if (_prefill_rope_fused and qkv.is_cuda and qkv.dim() == 2 and m.num_prefill_tokens
                 and not m.num_decodes and self.q_norm is None and self.k_norm is None
                 and m.num_prefill_tokens == qkv.shape[0]):
@@ -139,7 +140,7 @@ class LlamaAttention(nn.Module):
                               None if self.q_norm is None else self.q_norm.weight,
                               None if self.k_norm is None else self.k_norm.weight,
                               self.cfg.rms_eps, k_scale=ctx.k_scale, v_scale=ctx.v_scale,
-                              dtype=self.qkv_proj.weight.dtype)
+                              dtype=self.dtype)
         return self.attn(q, ctx)
 
 
@@ -181,6 +182,7 @@ class LlamaForCausalLM(nn.Module):
         super().__init__()
         self.cfg = cfg
         self.dtype = dtype
+        self.quantization = None     # "fp8" once models/quant.py quantize_model has run
         s = get_state()
         self.start, self.end = pp_layer_range(cfg.num_layers, s.pp_size, s.pp_rank)
         self.first, self.last = s.is_first_pp, s.is_last_pp
@@ -462,7 +464,8 @@ class LlamaForCausalLM(nn.Module):
     def qkv_dims(self) -> dict:
         """(N, K) of the QKV weight -> (nq, nkv, head_dim) of its RoPE / KV-write consumer
         (ops/gemm.py tunes the K9m QKV GEMM with that kernel summing its K-slices)."""
-        if not self.layers or not hasattr(self.layers[0], "self_attn"):
+        if (not self.layers or not hasattr(self.layers[0], "self_attn")
+                or self.quantization is not None):
             return {}
         at = self.layers[0].self_attn
         if at.qkv_proj.bias is not None:
@@ -470,19 +473,24 @@ class LlamaForCausalLM(nn.Module):
         return {tuple(at.qkv_proj.weight.shape): (at.nq, at.nkv, self.cfg.head_dim)}
 
     def silu_weights(self) -> list:
-        """The merged gate_up weights (decode: silu_mul fused into their K9m GEMM)."""
+        """The merged gate_up weights (decode: silu_mul fused into their K9m GEMM).  The
+        bf16 fast paths' lists are empty on a quantised model (ops/gemm.py W8A16)."""
+        if self.quantization is not None:
+            return []
         return [l.mlp.gate_up_proj.weight for l in self.layers
                 if isinstance(getattr(l, "mlp", None), LlamaMLP)]
 
     def silu_shapes(self) -> set:
         """(N, K) of the merged gate_up weights (their split-K reduction carries silu_mul)."""
+        if self.quantization is not None:
+            return set()
         return {tuple(l.mlp.gate_up_proj.weight.shape) for l in self.layers
                 if isinstance(getattr(l, "mlp", None), LlamaMLP)}
 
     def tail_shapes(self) -> set:
         """(N, K) of the o / down projections whose split-K reduction the following
         residual add + RMSNorm absorbs (``_forward_tail_fused``), when that path can run."""
-        if not (self.first and self.last and self.layers
+        if not (self.first and self.last and self.layers and self.quantization is None
                 and get_state().tp_size == 1 and _tail_fusion_enabled):
             return set()
         l0 = self.layers[0]
@@ -500,7 +508,7 @@ class LlamaForCausalLM(nn.Module):
     def _fusable(self) -> bool:
         s = get_state()
         return (self.first and self.last and s.tp_size == 1 and not self.cfg.is_moe
-                and ops.fused_small_m_enabled())
+                and self.quantization is None and ops.fused_small_m_enabled())
 
     def _forward_fused(self, input_ids, positions, ctx, cfgs):
         """The decoder at small M with the residual stream kept in one buffer: every

@@ -25,6 +25,7 @@ import torch.nn.functional as F
 log = logging.getLogger("kgc.gemm")
 
 SKINNY_MAX_M = 64
+_FP8 = torch.float8_e4m3fn      # a --quantization fp8 weight (ops/quant.py)
 # (mt, nt, nw, ntl) configurations the tuner tries; mt = 16-row batch tiles.
 _CONFIGS = [(mt, nt, nw, ntl) for mt in (1, 2, 4) for nt in (1, 2) for nw in (4, 8, 16)
             for ntl in (True, False)]
@@ -90,6 +91,210 @@ def _packed_put(w: torch.Tensor, silu: bool, p: torch.Tensor) -> None:
             del _packed[key]
     _packed[key] = (weakref.ref(w, drop), p)
 _PACK_FRACTION = float(os.environ.get("KGC_DGEMM_PACK_FRACTION", "0.25"))
+
+
+# ------------------------------------------------------------------ W8A16 (--quantization fp8)
+# fp8 weights (ops/quant.py) never meet the bf16 plans above, which are keyed by (M, N, K)
+# only: every entry point below checks the weight's dtype first.
+#   M <= 64: K9q (csrc/kernels/gemm_w8.hip), or -- where start-up timing measured it faster,
+#            or no K9q configuration fits the shape -- the widen path;
+#   M  > 64: the widen path: kgc.w8_widen writes round(w8 * scale) into a static per-device
+#            scratch and the library GEMM runs on it (correct and graph-capturable, but it
+#            moves MORE bytes than a bf16 weight would: 1 read + 2 written + 2 read per
+#            element).
+# (M, N, K) -> K9q cfg, or None where the widen path measured faster
+_plan_w8: dict[tuple[int, int, int], Optional[tuple]] = {}
+# merged gate_up (M, 2I, K) -> cfg of K9q's SiLU form, where it beat the plan + silu_mul
+_plan_w8_silu: dict[tuple[int, int, int], Optional[tuple]] = {}
+_w8_scratch: dict[tuple, torch.Tensor] = {}
+_w8_scratch_old: list = []      # outgrown scratches stay alive: captured graphs write them
+_w8_counts = {"k9q": 0, "k9q_silu": 0, "widen": 0}
+_w8_enabled = os.environ.get("KGC_W8_GEMM", "1") != "0"
+# K9q configurations: K9's, except (4, 2, 16), which does not fit 128 VGPRs per lane
+_W8_CONFIGS = [c for c in _CONFIGS if c[:3] != (4, 2, 16)]
+
+
+def w8_ok(M: int, N: int, K: int, cfg) -> bool:
+    """Shapes K9q takes at this configuration: a lane loads 16 e4m3 per k-pair, so each of
+    the NW waves needs a K-range that is a multiple of 64."""
+    mt, nt, nw, _ = cfg
+    return (1 <= M <= 16 * mt and N % (16 * nt) == 0 and K % (64 * nw) == 0
+            and (mt, nt, nw) != (4, 2, 16))
+
+
+def w8_default_cfg(M: int, N: int, K: int, silu: bool = False):
+    """The fixed configuration of an engine without a plan (eager engines, tests): the
+    smallest batch tile that holds M, 4 waves, non-temporal loads; None if it does not fit."""
+    cfg = (1 if M <= 16 else (2 if M <= 32 else 4), 2 if silu else 1, 4, True)
+    return cfg if w8_ok(M, N, K, cfg) and (not silu or N % 32 == 0) else None
+
+
+def w8_gemm(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor,
+            bias: Optional[torch.Tensor], cfg, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K9q: (x W8^T) * scale (+ bias) in x's dtype."""
+    from . import _k
+    if out is None:
+        out = torch.empty(x.shape[0], w8.shape[0], dtype=x.dtype, device=x.device)
+    _k().w8_gemm(out, x, w8, scale, bias, *cfg, False)
+    _w8_counts["k9q"] += 1
+    return out
+
+
+def w8_silu(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, cfg,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K9q's SiLU form over a merged [gate; up] fp8 weight [2I, K]: out [M, I]."""
+    from . import _k
+    if out is None:
+        out = torch.empty(x.shape[0], w8.shape[0] // 2, dtype=x.dtype, device=x.device)
+    _k().w8_gemm(out, x, w8, scale, None, *cfg, True)
+    _w8_counts["k9q_silu"] += 1
+    return out
+
+
+def w8_reserve(device: torch.device, numel: int, dtype: torch.dtype) -> torch.Tensor:
+    """The widen path's scratch on ``device``: at least ``numel`` elements of ``dtype``.
+    The engine reserves the largest quantised weight before graphs are captured."""
+    key = (device, dtype)
+    s = _w8_scratch.get(key)
+    if s is None or s.numel() < numel:
+        if s is not None:
+            _w8_scratch_old.append(s)
+        s = _w8_scratch[key] = torch.empty(numel, dtype=dtype, device=device)
+    return s
+
+
+def w8_widen(w8: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """round(w8 * scale) as a [N, K] view of the device's scratch (valid until the next call)."""
+    from . import _k
+    N, K = w8.shape
+    out = w8_reserve(w8.device, N * K, dtype)[: N * K].view(N, K)
+    _k().w8_widen(out, w8, scale)
+    return out
+
+
+def w8_widen_linear(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor,
+                    bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _w8_counts["widen"] += 1
+    return F.linear(x, w8_widen(w8, scale, x.dtype), bias)
+
+
+def _w8_x_ok(x: torch.Tensor) -> bool:
+    return (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 8 == 0
+            and x.data_ptr() % 16 == 0 and x.dtype in (torch.bfloat16, torch.float16))
+
+
+def w8_linear(x: torch.Tensor, w8: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A quantised linear layer.  CPU (the oracle, and what the CPU suite runs):
+    x @ (w8.float() * scale[:, None]).T in the activation dtype."""
+    from .quant import dequantize_fp8_rows, w8_scale
+    scale = w8_scale(w8)
+    if not x.is_cuda:
+        return F.linear(x, dequantize_fp8_rows(w8, scale, x.dtype), bias)
+    if x.dim() != 2:
+        return w8_linear(x.reshape(-1, x.shape[-1]), w8, bias).view(*x.shape[:-1], w8.shape[0])
+    M, (N, K) = x.shape[0], w8.shape
+    if _w8_enabled and 1 <= M <= SKINNY_MAX_M and _w8_x_ok(x):
+        key = (M, N, K)
+        cfg = _plan_w8[key] if key in _plan_w8 else w8_default_cfg(M, N, K)
+        if cfg is not None:
+            return w8_gemm(x, w8, scale, bias, cfg)
+    return w8_widen_linear(x, w8, scale, bias)
+
+
+def w8_linear_silu(x: torch.Tensor, w8: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    from . import silu_mul
+    from .quant import w8_scale
+    if (_w8_enabled and bias is None and x.is_cuda and _w8_x_ok(x)
+            and 1 <= x.shape[0] <= SKINNY_MAX_M):
+        key = (x.shape[0], w8.shape[0], w8.shape[1])
+        cfg = _plan_w8_silu[key] if key in _plan_w8_silu else w8_default_cfg(*key, silu=True)
+        if cfg is not None:
+            return w8_silu(x, w8, w8_scale(w8), cfg)
+    return silu_mul(w8_linear(x, w8, bias))
+
+
+def w8_plan() -> dict:
+    return dict(_plan_w8)
+
+
+def w8_silu_plan() -> dict:
+    return dict(_plan_w8_silu)
+
+
+def w8_counts() -> dict:
+    """Calls of each quantised path so far (a captured graph counts once, at capture)."""
+    return dict(_w8_counts)
+
+
+@torch.inference_mode()
+def tune_w8(weights: Iterable[torch.Tensor], ms: Iterable[int], dtype: torch.dtype,
+            silu_shapes=(), reps: int = 3) -> dict:
+    """For each fp8 weight shape and decode bucket M <= 64: every K9q configuration against
+    the widen path, graph-replayed over ALL weights of the shape (HBM-resident, as in a
+    decode step); the faster goes into the W8 plan.  ``silu_shapes``: (N, K) of merged
+    gate_up weights, whose SiLU form is timed against the plain winner + silu_mul.
+    Returns {(M, N, K): (chosen cfg or None, widen us, best K9q us, best K9q cfg)}."""
+    from . import silu_mul
+    from .quant import is_fp8, w8_scale
+    if not _w8_enabled:
+        return {}
+    by_shape: dict[tuple[int, int], list[torch.Tensor]] = {}
+    for w in weights:
+        if w.is_cuda and w.dim() == 2 and is_fp8(w):
+            by_shape.setdefault((w.shape[0], w.shape[1]), []).append(w)
+    res = {}
+    for (N, K), ws in sorted(by_shape.items()):
+        sc = [w8_scale(w) for w in ws]
+        for M in sorted(set(m for m in ms if 1 <= m <= SKINNY_MAX_M)):
+            x = torch.randn(M, K, dtype=dtype, device=ws[0].device)
+            out = torch.empty(M, N, dtype=x.dtype, device=x.device)
+
+            def wide():
+                for w, s in zip(ws, sc):
+                    w8_widen_linear(x, w, s)
+            wide_t = _time_graphed(wide, reps)
+            best_t, best = float("inf"), None
+            for cfg in _W8_CONFIGS:
+                if not w8_ok(M, N, K, cfg) or (cfg[0] > 1 and M <= 16 * (cfg[0] // 2)):
+                    continue
+
+                def fn(cfg=cfg):
+                    for w, s in zip(ws, sc):
+                        w8_gemm(x, w, s, None, cfg, out)
+                t = _time_graphed(fn, reps)
+                if t < best_t:
+                    best_t, best = t, cfg
+            chosen = best if best_t < wide_t else None
+            _plan_w8[(M, N, K)] = chosen
+            n = len(ws)
+            res[(M, N, K)] = (chosen, wide_t * 1e3 / n, best_t * 1e3 / n, best)
+            log.info("gemm W8 M=%d N=%d K=%d: widen + hipBLASLt %.1f us, K9q %s %.1f us -> %s",
+                     M, N, K, wide_t * 1e3 / n, best, best_t * 1e3 / n,
+                     "K9q" if chosen else "widen")
+            if (N, K) not in silu_shapes or N % 32:
+                continue
+            act = torch.empty(M, N // 2, dtype=x.dtype, device=x.device)
+
+            def sep():
+                for w in ws:
+                    silu_mul(w8_linear(x, w), act)
+            sep_t = _time_graphed(sep, reps)
+            sbest_t, sbest = float("inf"), None
+            for cfg in _W8_CONFIGS:
+                if (cfg[1] != 2 or not w8_ok(M, N, K, cfg)
+                        or (cfg[0] > 1 and M <= 16 * (cfg[0] // 2))):
+                    continue
+
+                def fn(cfg=cfg):
+                    for w, s in zip(ws, sc):
+                        w8_silu(x, w, s, cfg, act)
+                t = _time_graphed(fn, reps)
+                if t < sbest_t:
+                    sbest_t, sbest = t, cfg
+            _plan_w8_silu[(M, N, K)] = sbest if sbest_t < sep_t else None
+            log.info("gemm W8 M=%d N=%d K=%d silu: plan + silu_mul %.1f us, K9q SiLU %s %.1f us",
+                     M, N, K, sep_t * 1e3 / n, sbest, sbest_t * 1e3 / n)
+    return res
 
 
 def _dg_info(cfg: int):
@@ -185,6 +390,8 @@ def linear_silu(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     at this (M, N, K) the activation is the GEMM's epilogue (S = 1) or rides the split-K
     reduction (``splitk_reduce_silu``), so the [M, 2I] gate_up output never exists."""
     from . import _k, silu_mul
+    if w.dtype == _FP8:
+        return w8_linear_silu(x, w, bias)
     if bias is None and x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and _plan_silu:
         cfg = _plan_silu.get((x.shape[0], w.shape[0], w.shape[1]))
         if cfg is not None:
@@ -206,6 +413,8 @@ def linear_qkv(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     """The QKV projection for the fused RoPE / KV-write kernel: x W^T, or -- where the plan
     runs K9m split-K at this (M, N, K) -- its fp32 K-slices [S, M, N], which that kernel
     sums (``ops.rope_kv_write``), so the reduction needs no launch of its own."""
+    if w.dtype == _FP8:
+        return w8_linear(x, w)
     p = _dg_plan(x, w, "qkv")
     if p is not None:
         cfg, S = p
@@ -220,6 +429,8 @@ def linear_add_rms(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor,
     plan runs K9m split-K at this (M, N, K), the slice reduction, residual add and norm are
     one kernel (``splitk_add_rms_norm``); otherwise the GEMM and ``fused_add_rms_norm``."""
     from . import _k, fused_add_rms_norm
+    if w.dtype == _FP8:
+        return fused_add_rms_norm(w8_linear(x, w), residual, gamma, eps)
     if _plan_accnorm and x.is_cuda and x.dim() == 2 and x.stride(1) == 1:
         cfg = _plan_accnorm.get((x.shape[0], w.shape[0], w.shape[1]))
         if cfg is not None and residual.is_contiguous():
@@ -254,6 +465,8 @@ def skinny_gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], 
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    if w.dtype == _FP8:
+        return w8_linear(x, w, bias)
     if x.is_cuda and x.dim() == 2 and x.shape[0] <= SKINNY_MAX_M and _plan:
         cfg = _plan.get((x.shape[0], w.shape[0], w.shape[1]))
         if cfg is not None and x.stride(1) == 1:
@@ -502,6 +715,8 @@ def save_dg_table(path: str, res: dict, meta: dict) -> int:
 
 
 def clear_plan() -> None:
+    _plan_w8.clear()
+    _plan_w8_silu.clear()
     _dg_table.clear()
     _best_sk.clear()
     _best_silu.clear()

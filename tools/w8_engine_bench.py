@@ -1,0 +1,65 @@
+"""Decode TPOT and KV blocks of one engine with and without ``--quantization fp8``.
+
+    python tools/w8_engine_bench.py [--model llama-3-8b] [--batches 1,16] [--quantization fp8]
+                                    [--input-len 128] [--output-len 128]
+
+Dummy weights, one GPU, graph-replayed decode.  One JSON line per batch size: the KV blocks
+the profile step reports and the mean time per output token of the decode steps (time from
+the first to the last generated token / tokens after the first).  Run it once without and
+once with ``--quantization fp8``, back to back on the same GPU.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="llama-3-8b")
+    ap.add_argument("--batches", default="1,16")
+    ap.add_argument("--quantization", default=None)
+    ap.add_argument("--input-len", type=int, default=128)
+    ap.add_argument("--output-len", type=int, default=128)
+    ap.add_argument("--blocks-only", action="store_true",
+                    help="report the KV block count and stop (no graphs, no decode)")
+    a = ap.parse_args()
+    from kubernetes_gpu_cluster_amd.engine.config import EngineConfig
+    from kubernetes_gpu_cluster_amd.engine.llm_engine import LLMEngine
+    from kubernetes_gpu_cluster_amd.engine.sequence import SamplingParams
+    batches = [int(b) for b in a.batches.split(",")]
+    eng = LLMEngine(EngineConfig(model=a.model, random_init=True, quantization=a.quantization,
+                                 max_model_len=4096, max_num_seqs=256,
+                                 max_num_batched_tokens=16384, cuda_graph_max_bs=max(batches),
+                                 enforce_eager=a.blocks_only))
+    base = {"model": a.model, "quantization": a.quantization, "kv_blocks": eng.num_blocks,
+            "weights_gb": round(sum(p.numel() * p.element_size()
+                                    for p in eng.executor.runner.model.parameters()) / 1e9, 2)}
+    if a.blocks_only:
+        print(json.dumps(base), flush=True)
+        return
+    g = torch.Generator().manual_seed(0)
+    for B in batches:
+        for rep in range(2):        # the first pass warms up
+            seqs = [eng.add_request(torch.randint(100, 100000, (a.input_len,), generator=g).tolist(),
+                                    SamplingParams(temperature=0.0, max_tokens=a.output_len,
+                                                   ignore_eos=True)) for _ in range(B)]
+            t_first = None
+            while eng.has_unfinished():
+                eng.step()
+                if t_first is None and all(len(s.output_token_ids) >= 1 for s in seqs):
+                    torch.cuda.synchronize()
+                    t_first, n_first = time.perf_counter(), min(len(s.output_token_ids) for s in seqs)
+            torch.cuda.synchronize()
+            t_end = time.perf_counter()
+        tpot = (t_end - t_first) / (a.output_len - n_first) * 1e3
+        print(json.dumps(dict(base, batch=B, tpot_ms=round(tpot, 3))), flush=True)
+
+
+if __name__ == "__main__":
+    main()
