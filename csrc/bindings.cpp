@@ -1271,6 +1271,91 @@ void w8_widen(Tensor out, Tensor W8, Tensor scale) {
                        W8.size(0), W8.size(1), stream());
 }
 
+// K9mq (gemm_w8_decode.hip): the K9m pipeline over packed e4m3 weights Wp [N/128, K/64, 8192]
+// (w8_dgemm_pack).  out fp32 [S, M, N] (epi 0), [M, N] (epi 1) or [M, N/2] (epi 2) in X's dtype.
+void w8_dgemm(Tensor C, Tensor X, Tensor Wp, Tensor scale, std::optional<Tensor> bias,
+              int64_t cfg, int64_t epi) {
+  check_gpu(X, "X");
+  check_same_dev(X, Wp, "Wp");
+  check_same_dev(X, C, "C");
+  check_same_dev(X, scale, "scale");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(X.device());
+  TORCH_CHECK(cfg >= 0 && cfg < kgc::w8_dgemm_num_cfgs(), "kgc.w8_dgemm: unknown tile config");
+  TORCH_CHECK(epi >= 0 && epi <= 2, "kgc.w8_dgemm: epi 0 (fp32 slices), 1 (out), 2 (silu pairs)");
+  int bm, bn, ns;
+  kgc::w8_dgemm_cfg_info((int)cfg, &bm, &bn, &ns);
+  TORCH_CHECK(X.scalar_type() == at::kBFloat16 || X.scalar_type() == at::kHalf,
+              "kgc.w8_dgemm: bf16/f16 X");
+  TORCH_CHECK((Wp.scalar_type() == at::kFloat8_e4m3fn || Wp.scalar_type() == at::kByte) &&
+              Wp.dim() == 3 && Wp.is_contiguous() && Wp.size(2) == 128 * 64,
+              "kgc.w8_dgemm: packed Wp [N/128, K/64, 8192] e4m3 / uint8 contiguous");
+  const int64_t N = Wp.size(0) * 128, K = Wp.size(1) * 64;
+  TORCH_CHECK(X.dim() == 2 && X.size(1) == K && X.stride(1) == 1 && X.stride(0) % 8 == 0 &&
+              X.stride(0) >= K && reinterpret_cast<uintptr_t>(X.data_ptr()) % 16 == 0,
+              "kgc.w8_dgemm: X [M, K], dense 16-B aligned rows");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(Wp.data_ptr()) % 16 == 0, "kgc.w8_dgemm: Wp alignment");
+  const int64_t M = X.size(0);
+  TORCH_CHECK(M > 64 && M <= 512, "kgc.w8_dgemm: 64 < M <= 512");
+  TORCH_CHECK(N >= 128 && N % bn == 0 && K >= 64 && N < ((int64_t)1 << 31) / 512 &&
+              K < ((int64_t)1 << 31) / 2, "kgc.w8_dgemm: N % 128 == 0, K % 64 == 0, size limits");
+  TORCH_CHECK(scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == N,
+              "kgc.w8_dgemm: scale fp32 [N]");
+  int64_t S = 1, ss = 0;
+  if (epi == 0) {
+    TORCH_CHECK(C.scalar_type() == at::kFloat && C.dim() == 3 && C.is_contiguous() &&
+                C.size(1) == M && C.size(2) == N, "kgc.w8_dgemm: C fp32 contiguous [S, M, N]");
+    S = C.size(0);
+    ss = C.stride(0);
+    TORCH_CHECK(S >= 1 && S <= 32 && S <= K / 64, "kgc.w8_dgemm: 1 <= S <= min(32, K / 64)");
+    TORCH_CHECK(!bias.has_value(), "kgc.w8_dgemm: no bias on fp32 slices");
+  } else {
+    TORCH_CHECK(epi != 2 || ((N / 2) % 64 == 0 && !bias.has_value()),
+                "kgc.w8_dgemm: silu epilogue needs (N/2) % 64 == 0 and no bias");
+    TORCH_CHECK(C.scalar_type() == X.scalar_type() && C.dim() == 2 && C.is_contiguous() &&
+                C.size(0) == M && C.size(1) == (epi == 2 ? N / 2 : N),
+                "kgc.w8_dgemm: C [M, N] (epi 1) or [M, N/2] (epi 2), contiguous, X's dtype");
+  }
+  TORCH_CHECK((M + bm - 1) / bm * (N / bn) * S < ((int64_t)1 << 31), "kgc.w8_dgemm: grid too large");
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N &&
+                bias->scalar_type() == X.scalar_type(), "kgc.w8_dgemm: bias [N] in X's dtype");
+    check_same_dev(X, *bias, "bias");
+    bp = bias->data_ptr();
+  }
+  kgc::launch_w8_dgemm(dt_code(X), (int)cfg, (int)epi, C.data_ptr(), X.data_ptr(), Wp.data_ptr(),
+                       scale.data_ptr<float>(), bp, (int)M, (int)N, (int)K, X.stride(0), (int)S,
+                       ss, stream());
+}
+
+// P [N/128, K/64, 8192] <- W8 [N, K] re-laid out for K9mq (silu: merged [gate; up])
+void w8_dgemm_pack(Tensor P, Tensor W8, bool silu) {
+  check_gpu(W8, "W8");
+  check_same_dev(W8, P, "P");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(W8.device());
+  TORCH_CHECK(W8.dim() == 2 && W8.is_contiguous() &&
+              (W8.scalar_type() == at::kFloat8_e4m3fn || W8.scalar_type() == at::kByte),
+              "kgc.w8_dgemm_pack: W8 [N, K] e4m3 / uint8 contiguous");
+  const int64_t N = W8.size(0), K = W8.size(1);
+  TORCH_CHECK(N % 128 == 0 && K % 64 == 0 && (!silu || (N / 2) % 64 == 0) &&
+              N * K < ((int64_t)1 << 40), "kgc.w8_dgemm_pack: N % 128, K % 64");
+  TORCH_CHECK(N <= INT32_MAX && K <= INT32_MAX, "kgc.w8_dgemm_pack: dims overflow");
+  TORCH_CHECK(P.scalar_type() == W8.scalar_type() && P.dim() == 3 && P.is_contiguous() &&
+              P.size(0) == N / 128 && P.size(1) == K / 64 && P.size(2) == 8192,
+              "kgc.w8_dgemm_pack: P [N/128, K/64, 8192] contiguous, W8's dtype");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(P.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(W8.data_ptr()) % 16 == 0, "kgc.w8_dgemm_pack: alignment");
+  kgc::launch_w8_dgemm_pack(silu, P.data_ptr(), W8.data_ptr(), (int)N, (int)K, stream());
+}
+
+int64_t w8_dgemm_num_cfgs() { return kgc::w8_dgemm_num_cfgs(); }
+std::vector<int64_t> w8_dgemm_cfg_info(int64_t cfg) {
+  TORCH_CHECK(cfg >= 0 && cfg < kgc::w8_dgemm_num_cfgs(), "kgc.w8_dgemm: unknown tile config");
+  int bm, bn, ns;
+  kgc::w8_dgemm_cfg_info((int)cfg, &bm, &bn, &ns);
+  return {bm, bn, ns};
+}
+
 void sample_stamps_enable(bool on) { kgc::sample_stamps_enable(on); }
 
 std::vector<int64_t> sample_stamps() {
@@ -1393,6 +1478,11 @@ TORCH_LIBRARY(kgc, m) {
   m.def("w8_gemm(Tensor(a!) C, Tensor X, Tensor W8, Tensor scale, Tensor? bias, int mt, int nt, "
         "int nw, bool ntl, bool silu=False) -> ()");
   m.def("w8_widen(Tensor(a!) out, Tensor W8, Tensor scale) -> ()");
+  m.def("w8_dgemm(Tensor(a!) C, Tensor X, Tensor Wp, Tensor scale, Tensor? bias, int cfg, "
+        "int epi) -> ()");
+  m.def("w8_dgemm_pack(Tensor(a!) P, Tensor W8, bool silu) -> ()");
+  m.def("w8_dgemm_num_cfgs() -> int", &w8_dgemm_num_cfgs);
+  m.def("w8_dgemm_cfg_info(int cfg) -> int[]", &w8_dgemm_cfg_info);
 }
 
 TORCH_LIBRARY_IMPL(kgc, CUDA, m) {
@@ -1432,4 +1522,6 @@ TORCH_LIBRARY_IMPL(kgc, CUDA, m) {
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("w8_gemm", &w8_gemm);
   m.impl("w8_widen", &w8_widen);
+  m.impl("w8_dgemm", &w8_dgemm);
+  m.impl("w8_dgemm_pack", &w8_dgemm_pack);
 }

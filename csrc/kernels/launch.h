@@ -115,6 +115,17 @@ void launch_w8_gemm(int dtype, int mt, int nt, int nw, bool ntl, bool silu, void
                     int N, int K, int64_t ldx, int64_t ldc, hipStream_t s);
 void launch_w8_widen(int dtype, void* out, const void* W, const float* scale, int64_t N,
                      int64_t K, hipStream_t s);
+// K9mq (gemm_w8_decode.hip): the K9m pipeline over packed e4m3 weights
+// Wp [N/128][K/64][128 x 64 B] (launch_w8_dgemm_pack; silu: gate / up 16-row groups
+// interleaved), 64 < M <= 512.  epi 0: fp32 slice z of C [S, M, N], each already scaled;
+// 1: C [M, N] = acc * scale (+ bias) (S = 1); 2: silu pairs of a SiLU-packed merged
+// [gate; up] weight into C [M, N/2] (S = 1).  w8_dgemm_cfg_info: BM, BN, ring slots.
+int w8_dgemm_num_cfgs();
+void w8_dgemm_cfg_info(int cfg, int* bm, int* bn, int* ns);
+void launch_w8_dgemm(int dtype, int cfg, int epi, void* C, const void* X, const void* Wp,
+                     const float* scale, const void* bias, int M, int N, int K, int64_t ldx,
+                     int S, int64_t slice_stride, hipStream_t s);
+void launch_w8_dgemm_pack(bool silu, void* P, const void* W8, int N, int K, hipStream_t s);
 
 // K13/K14 MoE: routing, expert bucketing, grouped MFMA GEMM, weighted combine.
 int moe_block_n();

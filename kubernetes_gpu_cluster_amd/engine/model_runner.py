@@ -718,11 +718,13 @@ class ModelRunner:
                              qkv_dims=getattr(self.model, "qkv_dims", lambda: {})(),
                              rs_shapes=getattr(self.model, "_rs_w", None) is not None)
             if getattr(self.model, "quantization", None) is not None:
-                # --quantization fp8: K9q's configurations against the widen path, per bucket
+                # --quantization fp8: K9q's (M <= 64) and K9mq's (M > 64) configurations
+                # against the widen path, per bucket
                 from ..models.quant import dense_projections
                 gu = {tuple(l.mlp.gate_up_proj.weight.shape) for l in self.model.layers}
                 gemm.tune_w8([m.weight for l in self.model.layers for m in dense_projections(l)],
-                             self.buckets, self.dtype, silu_shapes=gu)
+                             self.buckets, self.dtype, silu_shapes=gu,
+                             tail_shapes=getattr(self.model, "w8_tail_shapes", lambda: set())())
         whole = self.model.first and self.model.last
         if (not self.use_graphs or not (whole or self.pp_link is not None)
                 or not getattr(self.model, "graph_safe", True)):

@@ -131,6 +131,19 @@ class Worker:
             # packed or folded and before the KV pool is sized (models/quant.py)
             from ..models.quant import quantize_model
             quantize_model(self.model, cfg.quantization)
+            if dev.type == "cuda" and cfg.cuda_graph_max_bs > 64:
+                # packed e4m3 copies for K9mq at the decode buckets above 64 rows, eager and
+                # graph engines alike (the same kernels); they come out of the KV pool sized
+                # below (KGC_W8_DGEMM=0: none)
+                from ..models.quant import dense_projections
+                from ..ops import gemm
+                gu = [l.mlp.gate_up_proj.weight for l in self.model.layers]
+                skip = {id(w) for w in gu}
+                nb = gemm.pack_w8_decode_weights(
+                    [m.weight for l in self.model.layers for m in dense_projections(l)
+                     if id(m.weight) not in skip], gu)
+                log.info("quantization %s: %.2f GB of packed K9mq weight copies", cfg.quantization,
+                         nb / 1e9)
         if dev.type == "cuda" and not cfg.enforce_eager:
             # packed copies of the decode-GEMM weights for the K9m tiles, made before the
             # KV cache is sized so the pool accounts for them (ops/gemm.py)

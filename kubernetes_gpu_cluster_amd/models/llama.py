@@ -498,6 +498,15 @@ class LlamaForCausalLM(nn.Module):
             return {tuple(l0.self_attn.o_proj.weight.shape)}
         return {tuple(l0.self_attn.o_proj.weight.shape), tuple(l0.mlp.down_proj.weight.shape)}
 
+    def w8_tail_shapes(self) -> set:
+        """``tail_shapes`` of a quantised model: the o / down projections whose K9mq split-K
+        reduction the following residual add + RMSNorm absorbs (ops/gemm.py tune_w8)."""
+        if not (self.first and self.last and self.layers and self.quantization is not None
+                and get_state().tp_size == 1 and _tail_fusion_enabled and not self.cfg.is_moe):
+            return set()
+        l0 = self.layers[0]
+        return {tuple(l0.self_attn.o_proj.weight.shape), tuple(l0.mlp.down_proj.weight.shape)}
+
     def fused_norm_shapes(self) -> set:
         """(N, K) of the GEMMs whose input RMSNorm the fused layer absorbs (tuned at start)."""
         if not self._fusable or not self.layers:

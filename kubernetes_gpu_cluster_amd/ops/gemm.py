@@ -101,15 +101,26 @@ _PACK_FRACTION = float(os.environ.get("KGC_DGEMM_PACK_FRACTION", "0.25"))
 #   M  > 64: the widen path: kgc.w8_widen writes round(w8 * scale) into a static per-device
 #            scratch and the library GEMM runs on it (correct and graph-capturable, but it
 #            moves MORE bytes than a bf16 weight would: 1 read + 2 written + 2 read per
-#            element).
+#            element) -- except at the decode buckets with 64 < M <= 512 where the plan
+#            below names a K9mq configuration (csrc/kernels/gemm_w8_decode.hip: the K9m
+#            pipeline streaming packed e4m3 tiles, one byte per weight element).
 # (M, N, K) -> K9q cfg, or None where the widen path measured faster
 _plan_w8: dict[tuple[int, int, int], Optional[tuple]] = {}
 # merged gate_up (M, 2I, K) -> cfg of K9q's SiLU form, where it beat the plan + silu_mul
 _plan_w8_silu: dict[tuple[int, int, int], Optional[tuple]] = {}
 _w8_scratch: dict[tuple, torch.Tensor] = {}
 _w8_scratch_old: list = []      # outgrown scratches stay alive: captured graphs write them
-_w8_counts = {"k9q": 0, "k9q_silu": 0, "widen": 0}
+_w8_counts = {"k9q": 0, "k9q_silu": 0, "widen": 0, "k9mq": 0, "k9mq_silu": 0}
 _w8_enabled = os.environ.get("KGC_W8_GEMM", "1") != "0"
+# K9mq: (M, N, K, kind) -> (cfg, S), or None where the widen path (with the same consumer)
+# measured faster; kind as in _plan_dg ("plain" | "silu" | "tail").  No entry: widen.
+_plan_w8_dg: dict[tuple[int, int, int, str], Optional[tuple[int, int]]] = {}
+# KGC_W8_DGEMM: "1" tuned (default), "0" off (nothing packed, the widen path runs), "force"
+# (no timing: the first configuration in table order that fits, S = 1 -- tests, A/B runs)
+w8_dgemm_mode = os.environ.get("KGC_W8_DGEMM", "1")
+# packed e4m3 copies for K9mq: (data_ptr, silu) -> (weakref to the fp8 weight, packed tiles,
+# silu: the row scales in the packed tiles' row order, for the split-K slices)
+_w8_packed: dict[tuple[int, bool], tuple] = {}
 # K9q configurations: K9's, except (4, 2, 16), which does not fit 128 VGPRs per lane
 _W8_CONFIGS = [c for c in _CONFIGS if c[:3] != (4, 2, 16)]
 
@@ -198,6 +209,15 @@ def w8_linear(x: torch.Tensor, w8: torch.Tensor, bias: Optional[torch.Tensor] = 
         cfg = _plan_w8[key] if key in _plan_w8 else w8_default_cfg(M, N, K)
         if cfg is not None:
             return w8_gemm(x, w8, scale, bias, cfg)
+    p = _w8_dg_plan(x, w8, "plain")
+    if p is not None and (p[1] == 1 or bias is None):
+        cfg, S = p
+        if S == 1:
+            return w8_dgemm(x, w8, cfg, 1, bias=bias)
+        from . import _k
+        out = torch.empty(M, N, dtype=x.dtype, device=x.device)
+        _k().splitk_reduce(out, w8_dgemm(x, w8, cfg, S))
+        return out
     return w8_widen_linear(x, w8, scale, bias)
 
 
@@ -210,6 +230,15 @@ def w8_linear_silu(x: torch.Tensor, w8: torch.Tensor, bias: Optional[torch.Tenso
         cfg = _plan_w8_silu[key] if key in _plan_w8_silu else w8_default_cfg(*key, silu=True)
         if cfg is not None:
             return w8_silu(x, w8, w8_scale(w8), cfg)
+    p = _w8_dg_plan(x, w8, "silu") if bias is None and x.is_cuda else None
+    if p is not None:
+        cfg, S = p
+        if S == 1:
+            return w8_dgemm(x, w8, cfg, 1, epi=2)
+        from . import _k
+        out = torch.empty(x.shape[0], w8.shape[0] // 2, dtype=x.dtype, device=x.device)
+        _k().splitk_reduce_silu(out, w8_dgemm(x, w8, cfg, S, silu_w=True), True)
+        return out
     return silu_mul(w8_linear(x, w8, bias))
 
 
@@ -226,14 +255,250 @@ def w8_counts() -> dict:
     return dict(_w8_counts)
 
 
+# ------------------------------------------------------------------ K9mq (64 < M <= 512)
+_W8_DG_TILES: list = []          # (BM, BN, ring slots) per configuration id, read once
+
+
+def _w8_dg_tiles() -> list:
+    if not _W8_DG_TILES:
+        from . import _k
+        _W8_DG_TILES.extend(tuple(int(v) for v in _k().w8_dgemm_cfg_info(c))
+                            for c in range(int(_k().w8_dgemm_num_cfgs())))
+    return _W8_DG_TILES
+
+
+def w8_dg_ok(M: int, N: int, K: int, cfg: int = 0, S: int = 1) -> bool:
+    """Shapes K9mq takes: 64 < M <= 512, N in whole 128-column tiles, K in whole 64-k steps,
+    at most one K-slice per step (and the 32 slices the binding allows)."""
+    return (SKINNY_MAX_M < M <= DG_MAX_M and N >= 128 and N % 128 == 0 and K >= 64
+            and K % 64 == 0 and cfg >= 0 and 1 <= S <= min(32, K // 64))
+
+
+def w8_dg_plan() -> dict:
+    return dict(_plan_w8_dg)
+
+
+def _w8_packed_entry(w8: torch.Tensor, silu: bool) -> Optional[tuple]:
+    key = (w8.data_ptr(), silu)
+    e = _w8_packed.get(key)
+    if e is None:
+        return None
+    src = e[0]()
+    if src is None:
+        _w8_packed.pop(key, None)
+        return None
+    if src.data_ptr() != w8.data_ptr() or src.shape != w8.shape:
+        return None
+    return e
+
+
+def _w8_packed_get(w8: torch.Tensor, silu: bool) -> Optional[torch.Tensor]:
+    e = _w8_packed_entry(w8, silu)
+    return None if e is None else e[1]
+
+
+def _w8_packed_put(w8: torch.Tensor, silu: bool, p: torch.Tensor) -> None:
+    from .quant import tile_rows, w8_scale
+    key = (w8.data_ptr(), silu)
+    # the SiLU-packed tiles' columns are gate / up groups interleaved: a slice's column c
+    # is weight row tile_rows[c], so the slices take the scales in that order
+    sc = w8_scale(w8)[tile_rows(w8.shape[0], True, w8.device).flatten()].contiguous() if silu \
+        else None
+
+    def drop(ref, key=key):
+        e = _w8_packed.get(key)
+        if e is not None and e[0] is ref:
+            del _w8_packed[key]
+    _w8_packed[key] = (weakref.ref(w8, drop), p, sc)
+
+
+def w8_packed_weight(w8: torch.Tensor, silu: bool = False) -> Optional[torch.Tensor]:
+    return _w8_packed_get(w8, silu)
+
+
+def pack_w8_decode_weights(plain: Iterable[torch.Tensor], silu: Iterable[torch.Tensor]) -> int:
+    """Packed e4m3 copies ([N/128][K/64][128 rows x 64 B] tiles, ``quant.pack_fp8_tiles_reference``)
+    of a quantised model's decode-GEMM weights for K9mq, made once before the KV cache is
+    sized.  ``silu``: merged gate_up weights, packed with gate and up 16-row groups
+    interleaved.  Nothing is packed (the widen path stays) with KGC_W8_DGEMM=0 or when the
+    copies would exceed KGC_DGEMM_PACK_FRACTION of device memory.  Returns bytes packed."""
+    if w8_dgemm_mode == "0" or not _w8_enabled:
+        return 0
+    from . import _k
+    todo = []
+    for w, sl in [(w, False) for w in plain] + [(w, True) for w in silu]:
+        if (w.is_cuda and w.dim() == 2 and w.dtype == _FP8 and w.is_contiguous()
+                and w.shape[0] % 128 == 0 and w.shape[1] % 64 == 0
+                and (not sl or (w.shape[0] // 2) % 64 == 0) and _w8_packed_get(w, sl) is None):
+            todo.append((w, sl))
+    need = sum(w.numel() for w, _ in todo)
+    if not todo:
+        return 0
+    free, total = torch.cuda.mem_get_info(todo[0][0].device)
+    if need > _PACK_FRACTION * total or need > free - (8 << 30):
+        log.info("K9mq: %.1f GB of packed fp8 weights exceeds the budget; widen path only",
+                 need / 1e9)
+        return 0
+    for w, sl in todo:
+        N, K = w.shape
+        p = torch.empty(N // 128, K // 64, 8192, dtype=w.dtype, device=w.device)
+        _k().w8_dgemm_pack(p, w.detach(), sl)
+        _w8_packed_put(w, sl, p)
+    log.info("K9mq: packed %d fp8 decode weights (%.2f GB, out of the KV pool; "
+             "KGC_W8_DGEMM=0 returns them)", len(todo), need / 1e9)
+    return need
+
+
+def w8_dgemm(x: torch.Tensor, w8: torch.Tensor, cfg: int, S: int, epi: int = 1,
+             out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+             silu_w: bool = False) -> torch.Tensor:
+    """K9mq over ``w8``'s packed copy: S == 1 -> (x W8^T) * scale (+ bias) in x's dtype
+    (epi 1) or the SiLU pairs [M, N/2] of a merged gate_up weight (epi 2); S > 1 -> the
+    [S, M, N] fp32 K-slices, each already scaled (the caller's consumer sums them).
+    silu_w: slices of the SiLU-packed copy (``splitk_reduce_silu(interleaved=True)``)."""
+    from . import _k
+    from .quant import w8_scale
+    silu = epi == 2 or silu_w
+    e = _w8_packed_entry(w8, silu)
+    if e is None:
+        raise RuntimeError("K9mq: the weight has no packed copy (pack_w8_decode_weights)")
+    wp = e[1]
+    M, N = x.shape[0], w8.shape[0]
+    if S > 1:
+        if bias is not None:
+            raise RuntimeError("K9mq: no bias on split-K slices")
+        out = torch.empty(S, M, N, dtype=torch.float32, device=x.device) if out is None else out
+        _k().w8_dgemm(out, x, wp, e[2] if silu else w8_scale(w8), None, cfg, 0)
+    else:
+        if out is None:
+            out = torch.empty(M, N // 2 if epi == 2 else N, dtype=x.dtype, device=x.device)
+        _k().w8_dgemm(out, x, wp, w8_scale(w8), bias, cfg, epi)
+    _w8_counts["k9mq_silu" if silu else "k9mq"] += 1
+    return out
+
+
+def _w8_dg_plan(x: torch.Tensor, w8: torch.Tensor, kind: str):
+    """The K9mq (cfg, S) of this call, or None: no entry, a None entry, the knob off, an X
+    the kernel does not take, or a weight without its packed copy -> the widen path."""
+    if not _plan_w8_dg or w8_dgemm_mode == "0" or not x.is_cuda or not _w8_x_ok(x):
+        return None
+    p = _plan_w8_dg.get((x.shape[0], w8.shape[0], w8.shape[1], kind))
+    if p is None or _w8_packed_get(w8, kind == "silu") is None:
+        return None
+    return p
+
+
+def _w8_dg_candidates(M: int, N: int, K: int, kind: str):
+    tiles = _w8_dg_tiles()
+    out = []
+    for c, (bm, bn, _) in enumerate(tiles):
+        # 128-row blocks up to M = 128, 256-row blocks above (K9m's split)
+        if (bm == 128) != (M <= 128):
+            continue
+        wgs = ((M + bm - 1) // bm) * (N // bn)
+        for S in _DG_SPLITS:
+            if not w8_dg_ok(M, N, K, c, S) or (S > 1 and wgs * S > _DG_MAX_GRID):
+                continue
+            out.append((c, S))
+    return out
+
+
+def _tune_w8_dgemm(ws, N: int, K: int, ms, dtype, reps: int, res: dict, kind: str) -> None:
+    """The widen path vs the K9mq candidates at each M in ``ms``, over all weights of the
+    shape, each side timed WITH its consumer ("silu": SiLU-and-mul, "tail": residual add +
+    RMSNorm, "plain": the split-K reduction) on graph replays; an entry is made only where
+    K9mq measured faster (None otherwise).  KGC_W8_DGEMM=force: no timing."""
+    from . import _k, fused_add_rms_norm, silu_mul
+    from .quant import w8_scale
+    silu = kind == "silu"
+    if any(_w8_packed_get(w, silu) is None for w in ws):
+        return
+    dev = ws[0].device
+    sc = [w8_scale(w) for w in ws]
+    wps = [_w8_packed_get(w, silu) for w in ws]
+    sc_il = [_w8_packed_entry(w, silu)[2] for w in ws]      # silu slices: tile row order
+    for M in sorted(set(ms)):
+        if not w8_dg_ok(M, N, K) or (kind == "tail" and N > 8192):
+            continue
+        key = (M, N, K, kind)
+        if w8_dgemm_mode == "force":
+            first = next((c for c in range(len(_w8_dg_tiles())) if w8_dg_ok(M, N, K, c, 1)), None)
+            if first is not None:
+                _plan_w8_dg[key] = (first, 1)
+                res[key] = ((first, 1), float("nan"), float("nan"), (first, 1))
+            continue
+        x = torch.randn(M, K, dtype=dtype, device=dev)
+        res_t = torch.zeros(M, N, dtype=dtype, device=dev) if kind == "tail" else None
+        gamma = torch.ones(N, dtype=dtype, device=dev) if kind == "tail" else None
+        No = N // 2 if silu else N
+        red = torch.empty(M, No, dtype=dtype, device=dev)
+
+        def wide():
+            for w, s in zip(ws, sc):
+                y = w8_widen_linear(x, w, s)
+                if silu:
+                    silu_mul(y, red)
+                elif kind == "tail":
+                    fused_add_rms_norm(y, res_t, gamma, 1e-6)
+        timed = []
+        for cfg, S in _w8_dg_candidates(M, N, K, kind):
+            buf = (torch.empty(S, M, N, dtype=torch.float32, device=dev) if S > 1 else
+                   torch.empty(M, No, dtype=dtype, device=dev))
+
+            def run(cfg=cfg, S=S, buf=buf):
+                for wp, s in zip(wps, sc_il if silu and S > 1 else sc):
+                    if S == 1:
+                        _k().w8_dgemm(buf, x, wp, s, None, cfg, 2 if silu else 1)
+                        if kind == "tail":
+                            fused_add_rms_norm(buf, res_t, gamma, 1e-6)
+                    else:
+                        _k().w8_dgemm(buf, x, wp, s, None, cfg, 0)
+                        if silu:
+                            _k().splitk_reduce_silu(red, buf, True)
+                        elif kind == "tail":
+                            _k().splitk_add_rms_norm(red, buf, res_t, gamma, 1e-6)
+                        else:
+                            _k().splitk_reduce(red, buf)
+            timed.append((_time(run, reps), (cfg, S), run))
+        if not timed:
+            continue
+        # the few fastest and the widen path, re-timed as graph replays in interleaved
+        # rounds, the median decides (as _tune_dgemm)
+        timed.sort(key=lambda e: e[0])
+        top = timed[:_DG_REFINE]
+        rounds: dict = {c: [] for _, c, _ in top}
+        wide_r = []
+        wide_g = _graph_of(wide)
+        graphs = [(c, _graph_of(fn)) for _, c, fn in top]
+        for _ in range(_DG_REFINE_ROUNDS):
+            wide_r.append(_time(wide_g, reps))
+            for c, g in graphs:
+                rounds[c].append(_time(g, reps))
+        del graphs, wide_g
+        med = {c: sorted(v)[len(v) // 2] for c, v in rounds.items()}
+        best = min(med, key=med.get)
+        best_t, wide_t = med[best], sorted(wide_r)[len(wide_r) // 2]
+        n = len(ws)
+        chosen = best if best_t < wide_t else None
+        _plan_w8_dg[key] = chosen
+        res[key] = (chosen, wide_t * 1e3 / n, best_t * 1e3 / n, best)
+        log.info("gemm W8 M=%d N=%d K=%d %s: widen + hipBLASLt %.1f us, K9mq %s %.1f us -> %s",
+                 M, N, K, kind, wide_t * 1e3 / n, best, best_t * 1e3 / n,
+                 "K9mq" if chosen else "widen")
+
+
 @torch.inference_mode()
 def tune_w8(weights: Iterable[torch.Tensor], ms: Iterable[int], dtype: torch.dtype,
-            silu_shapes=(), reps: int = 3) -> dict:
+            silu_shapes=(), reps: int = 3, tail_shapes=()) -> dict:
     """For each fp8 weight shape and decode bucket M <= 64: every K9q configuration against
     the widen path, graph-replayed over ALL weights of the shape (HBM-resident, as in a
     decode step); the faster goes into the W8 plan.  ``silu_shapes``: (N, K) of merged
     gate_up weights, whose SiLU form is timed against the plain winner + silu_mul.
-    Returns {(M, N, K): (chosen cfg or None, widen us, best K9q us, best K9q cfg)}."""
+    Decode buckets with 64 < M <= 512: the K9mq candidates against the widen path, each
+    with its consumer (``_tune_w8_dgemm``; ``tail_shapes``: (N, K) of the o / down
+    projections that feed ``linear_add_rms``), for the weights ``pack_w8_decode_weights``
+    packed.  Returns {(M, N, K): (chosen cfg or None, widen us, best K9q us, best K9q cfg)}
+    and the same under (M, N, K, kind) for K9mq."""
     from . import silu_mul
     from .quant import is_fp8, w8_scale
     if not _w8_enabled:
@@ -243,7 +508,13 @@ def tune_w8(weights: Iterable[torch.Tensor], ms: Iterable[int], dtype: torch.dty
         if w.is_cuda and w.dim() == 2 and is_fp8(w):
             by_shape.setdefault((w.shape[0], w.shape[1]), []).append(w)
     res = {}
+    ms = list(ms)
     for (N, K), ws in sorted(by_shape.items()):
+        if w8_dgemm_mode != "0":
+            kind = ("silu" if (N, K) in silu_shapes else
+                    "tail" if (N, K) in tail_shapes else "plain")
+            _tune_w8_dgemm(ws, N, K, [m for m in ms if SKINNY_MAX_M < m <= DG_MAX_M], dtype,
+                           reps, res, kind)
         sc = [w8_scale(w) for w in ws]
         for M in sorted(set(m for m in ms if 1 <= m <= SKINNY_MAX_M)):
             x = torch.randn(M, K, dtype=dtype, device=ws[0].device)
@@ -430,6 +701,14 @@ def linear_add_rms(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor,
     one kernel (``splitk_add_rms_norm``); otherwise the GEMM and ``fused_add_rms_norm``."""
     from . import _k, fused_add_rms_norm
     if w.dtype == _FP8:
+        p = _w8_dg_plan(x, w, "tail") if x.is_cuda else None
+        if p is not None and w.shape[0] <= 8192 and residual.is_contiguous():
+            cfg, S = p
+            if S > 1:
+                out = torch.empty_like(residual)
+                _k().splitk_add_rms_norm(out, w8_dgemm(x, w, cfg, S), residual, gamma, eps)
+                return out, residual
+            return fused_add_rms_norm(w8_dgemm(x, w, cfg, 1), residual, gamma, eps)
         return fused_add_rms_norm(w8_linear(x, w), residual, gamma, eps)
     if _plan_accnorm and x.is_cuda and x.dim() == 2 and x.stride(1) == 1:
         cfg = _plan_accnorm.get((x.shape[0], w.shape[0], w.shape[1]))
@@ -715,6 +994,7 @@ def save_dg_table(path: str, res: dict, meta: dict) -> int:
 
 
 def clear_plan() -> None:
+    _plan_w8_dg.clear()
     _plan_w8.clear()
     _plan_w8_silu.clear()
     _dg_table.clear()
@@ -748,7 +1028,9 @@ def dgemm_plan_has_m(M: int, kind: str) -> bool:
 
 def tail_plan_has_m(M: int) -> bool:
     """A fused projection-tail plan at this M: K9m split-K (M > 64) or SK_ACC_NORM."""
-    return dgemm_plan_has_m(M, "tail") or any(k[0] == M for k in _plan_accnorm)
+    return (dgemm_plan_has_m(M, "tail") or any(k[0] == M for k in _plan_accnorm)
+            or any(k[0] == M and k[3] == "tail" and v is not None
+                   for k, v in _plan_w8_dg.items()))
 
 
 def accnorm_plan() -> dict:

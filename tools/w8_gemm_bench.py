@@ -8,7 +8,11 @@ decode step the weights stream from HBM, not the 256 MB Infinity Cache).  One JS
 per case:
   M <= 64: K9q's best configuration and the widen path against the bf16 side as the
            start-up tuner picks it (K9 skinny or hipBLASLt);
-  M  > 64: the widen + hipBLASLt path against plain bf16 hipBLASLt.
+  M  > 64: the widen + hipBLASLt path against plain bf16 hipBLASLt;
+  --mid-ms (64 < M <= 512, e.g. 128,256,512): the best K9mq configuration against the widen
+           path and against the bf16 side as the start-up tuner picks it (K9m or hipBLASLt),
+           each with the consumer the engine runs behind it (gate_up: SiLU-and-mul, o / down:
+           residual add + RMSNorm, qkv: none / the split-K reduction).
 """
 import argparse
 import json
@@ -28,6 +32,7 @@ def main():
     ap.add_argument("--ms", default="1,8,16,64")
     ap.add_argument("--big-ms", default="128,256,4096")
     ap.add_argument("--big-layers", type=int, default=8)
+    ap.add_argument("--mid-ms", default="")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from kubernetes_gpu_cluster_amd.models import configs
@@ -43,6 +48,8 @@ def main():
     dt = torch.bfloat16
     ms = [int(m) for m in a.ms.split(",") if m]
     big = [int(m) for m in a.big_ms.split(",") if m]
+    mid = [int(m) for m in a.mid_ms.split(",") if m]
+    kinds = {"qkv": "plain", "o": "tail", "gate_up": "silu", "down": "tail"}
     out = open(a.out, "w") if a.out else None
 
     def emit(rec):
@@ -71,6 +78,27 @@ def main():
                   "k9q_weight_TBps": round(N * K / k9q_us / 1e6, 2),
                   "bf16_weight_TBps": round(N * K * 2 / bf_us / 1e6, 2)})
         gemm.clear_plan()
+        if mid:
+            kind = kinds[name]
+            silu, tail = ({(N, K)} if kind == "silu" else set()), ({(N, K)} if kind == "tail" else set())
+            gemm.pack_decode_weights([] if silu else ws, ws if silu else [])
+            gemm.pack_w8_decode_weights([] if silu else [w for w, _ in q],
+                                        [w for w, _ in q] if silu else [])
+            bf = gemm.tune_skinny(ws, mid, reps=5, silu_shapes=silu, tail_shapes=tail)
+            w8 = gemm.tune_w8([w for w, _ in q], mid, dt, reps=5, silu_shapes=silu, tail_shapes=tail)
+            for M in mid:
+                chosen, lib_us, k9m_us, k9m_cfg = bf[(M, N, K, kind)]
+                w8_chosen, wide_us, k9mq_us, k9mq_cfg = w8[(M, N, K, kind)]
+                bf_us = k9m_us if chosen else lib_us
+                emit({"gemm": name, "kind": kind, "M": M, "N": N, "K": K,
+                      "bf16_path": "K9m" if chosen else "hipblaslt", "bf16_cfg_S": chosen,
+                      "bf16_us": round(bf_us, 2), "hipblaslt_us": round(lib_us, 2),
+                      "k9mq_cfg_S": k9mq_cfg, "k9mq_us": round(k9mq_us, 2),
+                      "widen_us": round(wide_us, 2), "w8_chosen": "K9mq" if w8_chosen else "widen",
+                      "k9mq_speedup_vs_widen": round(wide_us / k9mq_us, 3),
+                      "k9mq_speedup_vs_bf16": round(bf_us / k9mq_us, 3),
+                      "k9mq_weight_TBps": round(N * K / k9mq_us / 1e6, 2)})
+            gemm.clear_plan()
         nb = min(a.big_layers, a.layers)
         for M in big:
             x = torch.randn(M, K, dtype=dt, device=dev)
