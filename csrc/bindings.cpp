@@ -1271,6 +1271,81 @@ void w8_widen(Tensor out, Tensor W8, Tensor scale) {
                        W8.size(0), W8.size(1), stream());
 }
 
+// K9f (gemm_w4.hip): C = X . dq(W4)^T (+ bias), or silu(gate) * up over a merged weight.
+// W4 uint8 [N, K/2] (two e2m1 per byte), scales uint8 [N, K/32] (e8m0, one per 32 k of a row)
+void w4_gemm(Tensor C, Tensor X, Tensor W4, Tensor scales, std::optional<Tensor> bias,
+             int64_t mt, int64_t nt, int64_t nw, bool silu) {
+  check_gpu(X, "X");
+  check_same_dev(X, W4, "W4");
+  check_same_dev(X, C, "C");
+  check_same_dev(X, scales, "scales");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(X.device());
+  TORCH_CHECK(X.dim() == 2 && W4.dim() == 2 && C.dim() == 2 && scales.dim() == 2,
+              "kgc.w4_gemm: 2-D operands");
+  TORCH_CHECK(C.scalar_type() == X.scalar_type() &&
+              (X.scalar_type() == at::kBFloat16 || X.scalar_type() == at::kHalf),
+              "kgc.w4_gemm: bf16/f16 X and C of one dtype");
+  TORCH_CHECK(W4.scalar_type() == at::kByte && scales.scalar_type() == at::kByte,
+              "kgc.w4_gemm: W4 and scales must be uint8");
+  TORCH_CHECK(mt == 1 || mt == 2 || mt == 4, "kgc.w4_gemm: mt in {1,2,4}");
+  TORCH_CHECK(nt == 1 || nt == 2, "kgc.w4_gemm: nt in {1,2}");
+  TORCH_CHECK(nw == 2 || nw == 4 || nw == 8, "kgc.w4_gemm: nw in {2,4,8}");
+  TORCH_CHECK(!(mt == 4 && nt == 2 && nw == 8), "kgc.w4_gemm: (mt, nt, nw) = (4, 2, 8) is not built");
+  const int64_t M = X.size(0), K = X.size(1), N = W4.size(0);
+  TORCH_CHECK(M >= 1 && M <= 16 * mt, "kgc.w4_gemm: M must be in [1, 16*mt]");
+  TORCH_CHECK(K % (128 * nw) == 0, "kgc.w4_gemm: K % (128*nw) != 0");
+  TORCH_CHECK(W4.size(1) * 2 == K && W4.is_contiguous(), "kgc.w4_gemm: W4 [N, K/2] contiguous");
+  TORCH_CHECK(scales.size(0) == N && scales.size(1) * 32 == K && scales.is_contiguous(),
+              "kgc.w4_gemm: scales [N, K/32] contiguous");
+  TORCH_CHECK(N % (16 * nt) == 0, "kgc.w4_gemm: N % (16*nt) != 0");
+  TORCH_CHECK(X.stride(1) == 1 && X.stride(0) % 8 == 0 && X.stride(0) >= K,
+              "kgc.w4_gemm: X rows dense, 16B aligned");
+  if (silu) {   // merged [gate; up] weight [2I, K] -> C [M, I]
+    TORCH_CHECK(nt == 2 && !bias.has_value() && N % 32 == 0,
+                "kgc.w4_gemm: silu epilogue needs nt=2, no bias, N % 32 == 0");
+    TORCH_CHECK(C.size(0) == M && C.size(1) == N / 2 && C.stride(1) == 1,
+                "kgc.w4_gemm: silu epilogue writes C [M, N/2]");
+  } else {
+    TORCH_CHECK(C.size(0) == M && C.size(1) == N && C.stride(1) == 1, "kgc.w4_gemm: C [M, N]");
+  }
+  TORCH_CHECK(N <= INT32_MAX && K <= INT32_MAX, "kgc.w4_gemm: dims overflow");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(X.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(W4.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(scales.data_ptr()) % 4 == 0, "kgc.w4_gemm: alignment");
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N &&
+                bias->scalar_type() == X.scalar_type(), "kgc.w4_gemm: bias [N]");
+    check_same_dev(X, *bias, "bias");
+    bp = bias->data_ptr();
+  }
+  kgc::launch_w4_gemm(dt_code(X), (int)mt, (int)nt, (int)nw, silu, C.data_ptr(), X.data_ptr(),
+                      W4.data_ptr(), scales.data_ptr(), bp, (int)M, (int)N, (int)K, X.stride(0),
+                      C.stride(0), stream());
+}
+
+// out[n, k] = dq(W4)[n, k], exact: an mxfp4 weight widened for the library GEMM
+void w4_widen(Tensor out, Tensor W4, Tensor scales) {
+  check_gpu(W4, "W4");
+  check_same_dev(W4, out, "out");
+  check_same_dev(W4, scales, "scales");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(W4.device());
+  TORCH_CHECK(W4.dim() == 2 && W4.is_contiguous() && W4.scalar_type() == at::kByte,
+              "kgc.w4_widen: W4 [N, K/2] uint8 contiguous");
+  TORCH_CHECK(W4.size(1) % 16 == 0, "kgc.w4_widen: K % 32 != 0");
+  TORCH_CHECK(out.dim() == 2 && out.is_contiguous() && out.size(0) == W4.size(0) &&
+              out.size(1) == 2 * W4.size(1) &&
+              (out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kHalf),
+              "kgc.w4_widen: out [N, K] bf16/f16 contiguous");
+  TORCH_CHECK(scales.dim() == 2 && scales.scalar_type() == at::kByte && scales.is_contiguous() &&
+              scales.size(0) == W4.size(0) && scales.size(1) * 16 == W4.size(1),
+              "kgc.w4_widen: scales [N, K/32] uint8 contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(W4.data_ptr()) % 16 == 0, "kgc.w4_widen: alignment");
+  kgc::launch_w4_widen(dt_code(out), out.data_ptr(), W4.data_ptr(), scales.data_ptr(),
+                       W4.size(0), 2 * W4.size(1), stream());
+}
+
 // K9mq (gemm_w8_decode.hip): the K9m pipeline over packed e4m3 weights Wp [N/128, K/64, 8192]
 // (w8_dgemm_pack).  out fp32 [S, M, N] (epi 0), [M, N] (epi 1) or [M, N/2] (epi 2) in X's dtype.
 void w8_dgemm(Tensor C, Tensor X, Tensor Wp, Tensor scale, std::optional<Tensor> bias,
@@ -1478,6 +1553,9 @@ TORCH_LIBRARY(kgc, m) {
   m.def("w8_gemm(Tensor(a!) C, Tensor X, Tensor W8, Tensor scale, Tensor? bias, int mt, int nt, "
         "int nw, bool ntl, bool silu=False) -> ()");
   m.def("w8_widen(Tensor(a!) out, Tensor W8, Tensor scale) -> ()");
+  m.def("w4_gemm(Tensor(a!) C, Tensor X, Tensor W4, Tensor scales, Tensor? bias, int mt, int nt, "
+        "int nw, bool silu=False) -> ()");
+  m.def("w4_widen(Tensor(a!) out, Tensor W4, Tensor scales) -> ()");
   m.def("w8_dgemm(Tensor(a!) C, Tensor X, Tensor Wp, Tensor scale, Tensor? bias, int cfg, "
         "int epi) -> ()");
   m.def("w8_dgemm_pack(Tensor(a!) P, Tensor W8, bool silu) -> ()");
@@ -1522,6 +1600,8 @@ TORCH_LIBRARY_IMPL(kgc, CUDA, m) {
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("w8_gemm", &w8_gemm);
   m.impl("w8_widen", &w8_widen);
+  m.impl("w4_gemm", &w4_gemm);
+  m.impl("w4_widen", &w4_widen);
   m.impl("w8_dgemm", &w8_dgemm);
   m.impl("w8_dgemm_pack", &w8_dgemm_pack);
 }

@@ -127,6 +127,14 @@ void launch_w8_dgemm(int dtype, int cfg, int epi, void* C, const void* X, const 
                      int S, int64_t slice_stride, hipStream_t s);
 void launch_w8_dgemm_pack(bool silu, void* P, const void* W8, int N, int K, hipStream_t s);
 
+// K9f: weight-only MXFP4 skinny GEMM (gemm_w4.hip) over codes W [N, K/2] (two e2m1 per byte,
+// low nibble first) and e8m0 block scales S [N, K/32], and the exact widening to bf16/f16.
+void launch_w4_gemm(int dtype, int mt, int nt, int nw, bool silu, void* C, const void* X,
+                    const void* W, const void* S, const void* bias, int M, int N, int K,
+                    int64_t ldx, int64_t ldc, hipStream_t s);
+void launch_w4_widen(int dtype, void* out, const void* W, const void* S, int64_t N, int64_t K,
+                     hipStream_t s);
+
 // K13/K14 MoE: routing, expert bucketing, grouped MFMA GEMM, weighted combine.
 int moe_block_n();
 int moe_block_k();

@@ -21,7 +21,7 @@ _DTYPES = {"auto": None, "bfloat16": torch.bfloat16, "bf16": torch.bfloat16,
 
 
 KV_CACHE_DTYPES = ("auto", "bfloat16", "bf16", "float16", "fp16", "fp8", "fp8_e4m3")
-QUANTIZATION_METHODS = ("fp8",)
+QUANTIZATION_METHODS = ("fp8", "mxfp4")
 
 
 @dataclasses.dataclass
@@ -46,7 +46,7 @@ class EngineConfig:
     disable_custom_all_reduce: bool = False
     trust_remote_code: bool = False
     kv_cache_dtype: str = "auto"
-    quantization: Optional[str] = None    # None | fp8 (weight-only W8A16, models/quant.py)
+    quantization: Optional[str] = None    # None | fp8 (W8A16) | mxfp4 (W4A16), models/quant.py
     seed: int = 0
     random_init: bool = False
     num_gpu_blocks_override: Optional[int] = None
@@ -145,7 +145,10 @@ def add_engine_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
            "gate_up, down): half the weight bytes, so more KV blocks and a lighter weight "
            "stream at decode batches <= 64 (K9q).  Larger batches and prefill widen each "
            "weight back to the model dtype before the library GEMM, which moves MORE bytes "
-           "than unquantised weights would.  Not for MoE or OPT models")
+           "than unquantised weights would.  mxfp4: online round-to-nearest OCP MXFP4 "
+           "(W4A16, 4.25 bits per weight) of the same linears: a quarter of the weight bytes "
+           "and the K9f GEMM at decode batches <= 64; every larger batch and prefill take "
+           "the widen path; less accurate than fp8.  Not for MoE or OPT models")
     a("--seed", type=int, default=0)
     a("--random-init", action="store_true", help="random weights (offline benchmarking)")
     a("--load-format", type=str, default="auto", help="'dummy' == --random-init")

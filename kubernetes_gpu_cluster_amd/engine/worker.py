@@ -127,11 +127,12 @@ class Worker:
                                            seed=cfg.seed)
         _fault_perturb_shard(self.model, self.ps)
         if cfg.quantization is not None:
-            # this rank's dense projection weights -> fp8 + row scales, before anything is
-            # packed or folded and before the KV pool is sized (models/quant.py)
+            # this rank's dense projection weights -> fp8 + row scales or mxfp4 + block
+            # scales, before anything is packed or folded and before the KV pool is sized
+            # (models/quant.py)
             from ..models.quant import quantize_model
             quantize_model(self.model, cfg.quantization)
-            if dev.type == "cuda" and cfg.cuda_graph_max_bs > 64:
+            if cfg.quantization == "fp8" and dev.type == "cuda" and cfg.cuda_graph_max_bs > 64:
                 # packed e4m3 copies for K9mq at the decode buckets above 64 rows, eager and
                 # graph engines alike (the same kernels); they come out of the KV pool sized
                 # below (KGC_W8_DGEMM=0: none)

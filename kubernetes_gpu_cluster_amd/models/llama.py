@@ -182,7 +182,7 @@ class LlamaForCausalLM(nn.Module):
         super().__init__()
         self.cfg = cfg
         self.dtype = dtype
-        self.quantization = None     # "fp8" once models/quant.py quantize_model has run
+        self.quantization = None     # "fp8" / "mxfp4" once models/quant.py quantize_model has run
         s = get_state()
         self.start, self.end = pp_layer_range(cfg.num_layers, s.pp_size, s.pp_rank)
         self.first, self.last = s.is_first_pp, s.is_last_pp
@@ -499,9 +499,9 @@ class LlamaForCausalLM(nn.Module):
         return {tuple(l0.self_attn.o_proj.weight.shape), tuple(l0.mlp.down_proj.weight.shape)}
 
     def w8_tail_shapes(self) -> set:
-        """``tail_shapes`` of a quantised model: the o / down projections whose K9mq split-K
+        """``tail_shapes`` of an fp8 model: the o / down projections whose K9mq split-K
         reduction the following residual add + RMSNorm absorbs (ops/gemm.py tune_w8)."""
-        if not (self.first and self.last and self.layers and self.quantization is not None
+        if not (self.first and self.last and self.layers and self.quantization == "fp8"
                 and get_state().tp_size == 1 and _tail_fusion_enabled and not self.cfg.is_moe):
             return set()
         l0 = self.layers[0]

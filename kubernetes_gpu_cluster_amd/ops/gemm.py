@@ -255,6 +255,202 @@ def w8_counts() -> dict:
     return dict(_w8_counts)
 
 
+# ------------------------------------------------------------------ W4A16 (--quantization mxfp4)
+# An mxfp4 weight (ops/quant.py) is uint8 codes [N, K/2] carrying its e8m0 block scales
+# [N, K/32]: K is 2 * shape[1] here and nowhere else.  Like fp8 weights it never meets the
+# bf16 plans: every entry point checks the weight's dtype first.
+#   M <= 64: K9f (csrc/kernels/gemm_w4.hip), or -- where start-up timing measured it faster,
+#            or no K9f configuration fits the shape -- the widen path;
+#   M  > 64, prefill: the widen path: kgc.w4_widen writes the exact dequantised weight into
+#            the static scratch fp8 uses (one per device and dtype) and the library GEMM
+#            runs on it.  It moves more bytes than a bf16 weight would.
+# (M, N, K) -> K9f cfg (mt, nt, nw), or None where the widen path measured faster
+_plan_w4: dict[tuple[int, int, int], Optional[tuple]] = {}
+# merged gate_up (M, 2I, K) -> cfg of K9f's SiLU form, where it beat the plan + silu_mul
+_plan_w4_silu: dict[tuple[int, int, int], Optional[tuple]] = {}
+_w4_counts = {"k9f": 0, "k9f_silu": 0, "widen": 0}
+_w4_enabled = os.environ.get("KGC_W4_GEMM", "1") != "0"
+_U8 = torch.uint8
+# K9f configurations (mt, nt, nw); (4, 2, 8) is not built (64 KB of LDS partial sums)
+_W4_CONFIGS = [(mt, nt, nw) for mt in (1, 2, 4) for nt in (1, 2) for nw in (2, 4, 8)
+               if (mt, nt, nw) != (4, 2, 8)]
+
+
+def w4_ok(M: int, N: int, K: int, cfg) -> bool:
+    """Shapes K9f takes at this configuration: a 16-byte weight load is one 32-element scale
+    block per lane, 128 k per wave, so each of the NW waves needs a K-range that is a
+    multiple of 128."""
+    mt, nt, nw = cfg
+    return (1 <= M <= 16 * mt and N % (16 * nt) == 0 and K % (128 * nw) == 0
+            and tuple(cfg) in _W4_CONFIGS)
+
+
+def w4_default_cfg(M: int, N: int, K: int, silu: bool = False):
+    """The fixed configuration of an engine without a plan (eager engines, tests): the
+    smallest batch tile that holds M, and 4 waves where each then has whole 512-k steps,
+    else 2; None if neither fits."""
+    mt, nt = 1 if M <= 16 else (2 if M <= 32 else 4), 2 if silu else 1
+    for cfg in ((mt, nt, 4), (mt, nt, 2)):
+        if (w4_ok(M, N, K, cfg) and (cfg[2] == 2 or K % 2048 == 0)
+                and (not silu or N % 32 == 0)):
+            return cfg
+    return None
+
+
+def w4_gemm(x: torch.Tensor, w4: torch.Tensor, scales: torch.Tensor,
+            bias: Optional[torch.Tensor], cfg, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K9f: x dq(W4)^T (+ bias) in x's dtype."""
+    from . import _k
+    if out is None:
+        out = torch.empty(x.shape[0], w4.shape[0], dtype=x.dtype, device=x.device)
+    _k().w4_gemm(out, x, w4, scales, bias, *cfg, False)
+    _w4_counts["k9f"] += 1
+    return out
+
+
+def w4_silu(x: torch.Tensor, w4: torch.Tensor, scales: torch.Tensor, cfg,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """K9f's SiLU form over a merged [gate; up] mxfp4 weight [2I, K]: out [M, I]."""
+    from . import _k
+    if out is None:
+        out = torch.empty(x.shape[0], w4.shape[0] // 2, dtype=x.dtype, device=x.device)
+    _k().w4_gemm(out, x, w4, scales, None, *cfg, True)
+    _w4_counts["k9f_silu"] += 1
+    return out
+
+
+def w4_widen(w4: torch.Tensor, scales: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """The exact dequantised weight as a [N, K] view of the device's scratch (the one
+    ``w8_reserve`` keeps; valid until the next widen of either method)."""
+    from . import _k
+    N, K = w4.shape[0], 2 * w4.shape[1]
+    out = w8_reserve(w4.device, N * K, dtype)[: N * K].view(N, K)
+    _k().w4_widen(out, w4, scales)
+    return out
+
+
+def w4_widen_linear(x: torch.Tensor, w4: torch.Tensor, scales: torch.Tensor,
+                    bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _w4_counts["widen"] += 1
+    return F.linear(x, w4_widen(w4, scales, x.dtype), bias)
+
+
+def w4_linear(x: torch.Tensor, w4: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """An mxfp4 linear layer.  CPU (the oracle, and what the CPU suite runs): F.linear on
+    the dequantised weight in the activation dtype."""
+    from .quant import dequantize_mxfp4, w4_scale
+    scales = w4_scale(w4)
+    if not x.is_cuda:
+        return F.linear(x, dequantize_mxfp4(w4, scales, x.dtype), bias)
+    N, K = w4.shape[0], 2 * w4.shape[1]
+    if x.dim() != 2:
+        return w4_linear(x.reshape(-1, x.shape[-1]), w4, bias).view(*x.shape[:-1], N)
+    M = x.shape[0]
+    if _w4_enabled and 1 <= M <= SKINNY_MAX_M and _w8_x_ok(x):
+        key = (M, N, K)
+        cfg = _plan_w4[key] if key in _plan_w4 else w4_default_cfg(M, N, K)
+        if cfg is not None:
+            return w4_gemm(x, w4, scales, bias, cfg)
+    return w4_widen_linear(x, w4, scales, bias)
+
+
+def w4_linear_silu(x: torch.Tensor, w4: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    from . import silu_mul
+    from .quant import w4_scale
+    if (_w4_enabled and bias is None and x.is_cuda and _w8_x_ok(x)
+            and 1 <= x.shape[0] <= SKINNY_MAX_M):
+        key = (x.shape[0], w4.shape[0], 2 * w4.shape[1])
+        cfg = _plan_w4_silu[key] if key in _plan_w4_silu else w4_default_cfg(*key, silu=True)
+        if cfg is not None:
+            return w4_silu(x, w4, w4_scale(w4), cfg)
+    return silu_mul(w4_linear(x, w4, bias))
+
+
+def w4_plan() -> dict:
+    return dict(_plan_w4)
+
+
+def w4_silu_plan() -> dict:
+    return dict(_plan_w4_silu)
+
+
+def w4_counts() -> dict:
+    """Calls of each mxfp4 path so far (a captured graph counts once, at capture)."""
+    return dict(_w4_counts)
+
+
+@torch.inference_mode()
+def tune_w4(weights: Iterable[torch.Tensor], ms: Iterable[int], dtype: torch.dtype,
+            silu_shapes=(), reps: int = 3) -> dict:
+    """For each mxfp4 weight shape and decode bucket M <= 64: every K9f configuration against
+    the widen path, graph-replayed over ALL weights of the shape (HBM-resident, as in a
+    decode step); the faster goes into the W4 plan.  ``silu_shapes``: (N, K) of merged
+    gate_up weights, whose SiLU form is timed against the plain winner + silu_mul.  Buckets
+    above 64 have no mxfp4 kernel yet: they take the widen path without a plan entry.
+    Returns {(M, N, K): (chosen cfg or None, widen us, best K9f us, best K9f cfg)}."""
+    from . import silu_mul
+    from .quant import is_mxfp4, w4_scale
+    if not _w4_enabled:
+        return {}
+    by_shape: dict[tuple[int, int], list[torch.Tensor]] = {}
+    for w in weights:
+        if w.is_cuda and w.dim() == 2 and is_mxfp4(w):
+            by_shape.setdefault((w.shape[0], 2 * w.shape[1]), []).append(w)
+    res = {}
+    for (N, K), ws in sorted(by_shape.items()):
+        sc = [w4_scale(w) for w in ws]
+        n = len(ws)
+        for M in sorted(set(m for m in ms if 1 <= m <= SKINNY_MAX_M)):
+            x = torch.randn(M, K, dtype=dtype, device=ws[0].device)
+            out = torch.empty(M, N, dtype=x.dtype, device=x.device)
+
+            def wide():
+                for w, s in zip(ws, sc):
+                    w4_widen_linear(x, w, s)
+            wide_t = _time_graphed(wide, reps)
+            best_t, best = float("inf"), None
+            for cfg in _W4_CONFIGS:
+                if not w4_ok(M, N, K, cfg) or (cfg[0] > 1 and M <= 16 * (cfg[0] // 2)):
+                    continue
+
+                def fn(cfg=cfg):
+                    for w, s in zip(ws, sc):
+                        w4_gemm(x, w, s, None, cfg, out)
+                t = _time_graphed(fn, reps)
+                if t < best_t:
+                    best_t, best = t, cfg
+            chosen = best if best_t < wide_t else None
+            _plan_w4[(M, N, K)] = chosen
+            res[(M, N, K)] = (chosen, wide_t * 1e3 / n, best_t * 1e3 / n, best)
+            log.info("gemm W4 M=%d N=%d K=%d: widen + hipBLASLt %.1f us, K9f %s %.1f us -> %s",
+                     M, N, K, wide_t * 1e3 / n, best, best_t * 1e3 / n,
+                     "K9f" if chosen else "widen")
+            if (N, K) not in silu_shapes or N % 32:
+                continue
+            act = torch.empty(M, N // 2, dtype=x.dtype, device=x.device)
+
+            def sep():
+                for w in ws:
+                    silu_mul(w4_linear(x, w), act)
+            sep_t = _time_graphed(sep, reps)
+            sbest_t, sbest = float("inf"), None
+            for cfg in _W4_CONFIGS:
+                if (cfg[1] != 2 or not w4_ok(M, N, K, cfg)
+                        or (cfg[0] > 1 and M <= 16 * (cfg[0] // 2))):
+                    continue
+
+                def fn(cfg=cfg):
+                    for w, s in zip(ws, sc):
+                        w4_silu(x, w, s, cfg, act)
+                t = _time_graphed(fn, reps)
+                if t < sbest_t:
+                    sbest_t, sbest = t, cfg
+            _plan_w4_silu[(M, N, K)] = sbest if sbest_t < sep_t else None
+            log.info("gemm W4 M=%d N=%d K=%d silu: plan + silu_mul %.1f us, K9f SiLU %s %.1f us",
+                     M, N, K, sep_t * 1e3 / n, sbest, sbest_t * 1e3 / n)
+    return res
+
+
 # ------------------------------------------------------------------ K9mq (64 < M <= 512)
 _W8_DG_TILES: list = []          # (BM, BN, ring slots) per configuration id, read once
 
@@ -663,6 +859,8 @@ def linear_silu(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     from . import _k, silu_mul
     if w.dtype == _FP8:
         return w8_linear_silu(x, w, bias)
+    if w.dtype == _U8:
+        return w4_linear_silu(x, w, bias)
     if bias is None and x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and _plan_silu:
         cfg = _plan_silu.get((x.shape[0], w.shape[0], w.shape[1]))
         if cfg is not None:
@@ -686,6 +884,8 @@ def linear_qkv(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     sums (``ops.rope_kv_write``), so the reduction needs no launch of its own."""
     if w.dtype == _FP8:
         return w8_linear(x, w)
+    if w.dtype == _U8:
+        return w4_linear(x, w)
     p = _dg_plan(x, w, "qkv")
     if p is not None:
         cfg, S = p
@@ -710,6 +910,8 @@ def linear_add_rms(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor,
                 return out, residual
             return fused_add_rms_norm(w8_dgemm(x, w, cfg, 1), residual, gamma, eps)
         return fused_add_rms_norm(w8_linear(x, w), residual, gamma, eps)
+    if w.dtype == _U8:
+        return fused_add_rms_norm(w4_linear(x, w), residual, gamma, eps)
     if _plan_accnorm and x.is_cuda and x.dim() == 2 and x.stride(1) == 1:
         cfg = _plan_accnorm.get((x.shape[0], w.shape[0], w.shape[1]))
         if cfg is not None and residual.is_contiguous():
@@ -746,6 +948,8 @@ def skinny_gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], 
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     if w.dtype == _FP8:
         return w8_linear(x, w, bias)
+    if w.dtype == _U8:
+        return w4_linear(x, w, bias)
     if x.is_cuda and x.dim() == 2 and x.shape[0] <= SKINNY_MAX_M and _plan:
         cfg = _plan.get((x.shape[0], w.shape[0], w.shape[1]))
         if cfg is not None and x.stride(1) == 1:
@@ -997,6 +1201,8 @@ def clear_plan() -> None:
     _plan_w8_dg.clear()
     _plan_w8.clear()
     _plan_w8_silu.clear()
+    _plan_w4.clear()
+    _plan_w4_silu.clear()
     _dg_table.clear()
     _best_sk.clear()
     _best_silu.clear()

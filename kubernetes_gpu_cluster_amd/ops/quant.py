@@ -1,4 +1,5 @@
-"""Weight-only FP8 (W8A16) quantisation of linear weights: ``--quantization fp8``.
+"""Weight-only quantisation of linear weights: ``--quantization fp8`` (W8A16, below) and
+``--quantization mxfp4`` (W4A16, OCP MXFP4: the second half of this file).
 
 A weight [N, K] becomes OCP e4m3 (``torch.float8_e4m3fn``) with one fp32 scale per output
 row: ``scale = amax(|row|) / 448``, so each row uses the whole e4m3 range, and
@@ -15,7 +16,7 @@ import torch
 
 FP8 = torch.float8_e4m3fn
 FP8_MAX = 448.0
-QUANTIZATION_METHODS = ("fp8",)
+QUANTIZATION_METHODS = ("fp8", "mxfp4")
 
 
 def quantize_fp8_rows(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
@@ -90,3 +91,82 @@ def pack_fp8_tiles_reference(w8: torch.Tensor, silu: bool = False) -> torch.Tens
     q = torch.arange(4, device=dev)[None, :] ^ swz[:, None]   # [r, position] -> k-chunk
     out = t[:, :, r[:, None], q]                              # [nb, kb, r, position, half, e]
     return out.reshape(N // 128, K // 64, 8192).contiguous()
+
+
+# ------------------------------------------------------------------ MXFP4 (--quantization mxfp4)
+# OCP MX v1.0, the layout published MXFP4 checkpoints use.  A weight [N, K] becomes
+#   codes  uint8 [N, K/2]:  element 2j is the low nibble of byte j, element 2j+1 the high one;
+#                           an e2m1 code is sign bit 3 and magnitude bits 2..0;
+#   scales uint8 [N, K/32]: e8m0 (biased exponent b, value 2^(b-127)), one per 32 consecutive
+#                           k of one row.
+# That is 4.25 bits per weight.  The GPU kernels (csrc/kernels/gemm_w4.hip) read this layout
+# directly (one copy on the device) and widen with the hardware conversion, which multiplies
+# by the power-of-two scale: the operand is the exact dequantised value.  The scales travel
+# with the codes as their ``w4_scale`` attribute.
+MXFP4_BLOCK = 32
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def mxfp4_exp_range(dtype: torch.dtype) -> tuple[int, int]:
+    """Unbiased block exponents for which every dequantised value (0.5 .. 6 times 2^e) is
+    exactly representable in ``dtype`` (and, for f16, normal): bf16 / fp32 [-126, 125],
+    f16 [-13, 13]."""
+    return (-13, 13) if dtype == torch.float16 else (-126, 125)
+
+
+def quantize_mxfp4(w: torch.Tensor, dtype=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """(codes uint8 [N, K/2], scales uint8 [N, K/32]) of a 2-D weight, on w's device.  Per
+    32-block: unbiased exponent e = floor(log2(amax)) - 2 (the OCP rule: amax lands in
+    [4, 8) before rounding), clamped to ``mxfp4_exp_range(dtype)`` (``dtype``: the dtype the
+    weight is dequantised to, w's own by default); elements w / 2^e rounded to nearest-even
+    on the e2m1 grid, saturating at +-6.  An all-zero block gets e = 0 and zero codes.
+    |w - dq| <= amax(block) / 4 (where e was not clamped)."""
+    assert w.dim() == 2 and w.shape[1] % MXFP4_BLOCK == 0, "quantize_mxfp4: [N, K], K % 32 == 0"
+    N, K = w.shape
+    lo, hi = mxfp4_exp_range(w.dtype if dtype is None else dtype)
+    wf = w.detach().float().view(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wf.abs().amax(dim=2)
+    ex = torch.frexp(amax)[1]                       # amax = m * 2^ex, m in [0.5, 1)
+    e = torch.where(amax > 0, (ex - 3).clamp(lo, hi), torch.zeros_like(ex))
+    a = torch.ldexp(wf.abs(), -e[:, :, None]).clamp_(max=6.0)
+    # nearest-even on the grid: spacing 0.5 below 2, 1 below 4, 2 up to 6 (torch.round is
+    # half-to-even, and the even multiples are the codes with a zero mantissa bit)
+    q = torch.where(a < 2, torch.round(a * 2) * 0.5,
+                    torch.where(a < 4, torch.round(a), torch.round(a * 0.5) * 2))
+    mag = torch.where(q < 2, q * 2, torch.where(q < 4, q + 2, q * 0.5 + 4)).to(torch.uint8)
+    code = (mag | (((wf < 0) & (q > 0)).to(torch.uint8) << 3)).view(N, K)
+    codes = (code[:, 0::2] | (code[:, 1::2] << 4)).contiguous()
+    scales = (e + 127).to(torch.uint8).contiguous()
+    return attach_w4_scale(codes, scales), scales
+
+
+def attach_w4_scale(codes: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    assert codes.dtype == torch.uint8 and scales.dtype == torch.uint8
+    assert codes.dim() == 2 and scales.shape == (codes.shape[0], codes.shape[1] // 16)
+    codes.w4_scale = scales  # type: ignore[attr-defined]
+    return codes
+
+
+def is_mxfp4(w: torch.Tensor) -> bool:
+    return w.dtype == torch.uint8 and getattr(w, "w4_scale", None) is not None
+
+
+def w4_scale(w4: torch.Tensor) -> torch.Tensor:
+    s = getattr(w4, "w4_scale", None)
+    if s is None:
+        raise RuntimeError("mxfp4 weight without its block scales (quantize_mxfp4 attaches them)")
+    return s
+
+
+def dequantize_mxfp4(codes: torch.Tensor, scales: torch.Tensor,
+                     dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """[N, K] ``dtype`` from codes [N, K/2] and scales [N, K/32], in plain torch: the CPU
+    path and the oracle of the GPU kernels.  The fp32 scale is built from the e8m0 byte as
+    ``b << 23``, as the kernels build it; value * scale is exact in fp32, and exact in
+    ``dtype`` for the exponents ``quantize_mxfp4`` produces for it."""
+    N, K = codes.shape[0], codes.shape[1] * 2
+    lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32,
+                       device=codes.device)
+    v = torch.stack([lut[(codes & 0xF).long()], lut[(codes >> 4).long()]], dim=-1)
+    sc = (scales.to(torch.int32) << 23).view(torch.float32)
+    return (v.view(N, K // MXFP4_BLOCK, MXFP4_BLOCK) * sc[:, :, None]).view(N, K).to(dtype)

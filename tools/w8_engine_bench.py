@@ -1,6 +1,6 @@
-"""Decode TPOT and KV blocks of one engine with and without ``--quantization fp8``.
+"""Decode TPOT and KV blocks of one engine with and without ``--quantization fp8 | mxfp4``.
 
-    python tools/w8_engine_bench.py [--model llama-3-8b] [--batches 1,16] [--quantization fp8]
+    python tools/w8_engine_bench.py [--model llama-3-8b] [--batches 1,16] [--quantization fp8|mxfp4]
                                     [--input-len 128] [--output-len 128]
 
 Dummy weights, one GPU, graph-replayed decode.  One JSON line per batch size: the KV blocks
@@ -9,7 +9,9 @@ the first to the last generated token / tokens after the first).  Run it once wi
 once with ``--quantization fp8``, back to back on the same GPU.  Batches above 64 (128, 256,
 512) run the mid-batch decode GEMMs: K9m for bf16 weights, K9mq or the widen path for fp8
 ones, and each line then carries the W8 plan of its bucket (``w8_plan``: shape and kind ->
-[cfg, S], or "widen").  ``--tag`` labels the lines, ``--out`` appends them to a file.
+[cfg, S], or "widen").  With ``--quantization mxfp4`` a line of a batch <= 64 carries the W4
+plan of its bucket (``w4_plan``: shape -> K9f [mt, nt, nw], or "widen"); larger batches take
+the widen path.  ``--tag`` labels the lines, ``--out`` appends them to a file.
 """
 import argparse
 import json
@@ -75,9 +77,14 @@ def main():
             t_end = time.perf_counter()
         tpot = (t_end - t_first) / (a.output_len - n_first) * 1e3
         rec = dict(base, batch=B, tpot_ms=round(tpot, 3))
-        if a.quantization and B > 64:
+        if a.quantization == "fp8" and B > 64:
             rec["w8_plan"] = {f"{N}x{K}:{kind}": list(v) if v else "widen"
                               for (M, N, K, kind), v in sorted(w8_plan.items()) if M == B}
+        if a.quantization == "mxfp4" and B <= 64:
+            rec["w4_plan"] = {f"{N}x{K}": list(v) if v else "widen"
+                              for (M, N, K), v in sorted(gemm.w4_plan().items()) if M == B}
+            rec["w4_silu_plan"] = {f"{N}x{K}": list(v) if v else "widen"
+                                   for (M, N, K), v in sorted(gemm.w4_silu_plan().items()) if M == B}
         emit(rec)
 
 
