@@ -1431,6 +1431,94 @@ std::vector<int64_t> w8_dgemm_cfg_info(int64_t cfg) {
   return {bm, bn, ns};
 }
 
+// K9mf (gemm_w4_decode.hip): the K9m pipeline over packed MXFP4 weights Wp [N/128, K/64, 4352]
+// (w4_dgemm_pack).  out fp32 [S, M, N] (epi 0), [M, N] (epi 1) or [M, N/2] (epi 2) in X's dtype.
+void w4_dgemm(Tensor C, Tensor X, Tensor Wp, std::optional<Tensor> bias, int64_t cfg,
+              int64_t epi) {
+  check_gpu(X, "X");
+  check_same_dev(X, Wp, "Wp");
+  check_same_dev(X, C, "C");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(X.device());
+  TORCH_CHECK(cfg >= 0 && cfg < kgc::w4_dgemm_num_cfgs(), "kgc.w4_dgemm: unknown tile config");
+  TORCH_CHECK(epi >= 0 && epi <= 2, "kgc.w4_dgemm: epi 0 (fp32 slices), 1 (out), 2 (silu pairs)");
+  int bm, bn, ns;
+  kgc::w4_dgemm_cfg_info((int)cfg, &bm, &bn, &ns);
+  TORCH_CHECK(X.scalar_type() == at::kBFloat16 || X.scalar_type() == at::kHalf,
+              "kgc.w4_dgemm: bf16/f16 X");
+  TORCH_CHECK(Wp.scalar_type() == at::kByte && Wp.dim() == 3 && Wp.is_contiguous() &&
+              Wp.size(2) == 128 * 32 + 256,
+              "kgc.w4_dgemm: packed Wp [N/128, K/64, 4352] uint8 contiguous");
+  const int64_t N = Wp.size(0) * 128, K = Wp.size(1) * 64;
+  TORCH_CHECK(X.dim() == 2 && X.size(1) == K && X.stride(1) == 1 && X.stride(0) % 8 == 0 &&
+              X.stride(0) >= K && reinterpret_cast<uintptr_t>(X.data_ptr()) % 16 == 0,
+              "kgc.w4_dgemm: X [M, K], dense 16-B aligned rows");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(Wp.data_ptr()) % 16 == 0, "kgc.w4_dgemm: Wp alignment");
+  const int64_t M = X.size(0);
+  TORCH_CHECK(M > 64 && M <= 512, "kgc.w4_dgemm: 64 < M <= 512");
+  TORCH_CHECK(N >= 128 && N % bn == 0 && K >= 64 && N < ((int64_t)1 << 31) / 512 &&
+              K < ((int64_t)1 << 31) / 2, "kgc.w4_dgemm: N % 128 == 0, K % 64 == 0, size limits");
+  int64_t S = 1, ss = 0;
+  if (epi == 0) {
+    TORCH_CHECK(C.scalar_type() == at::kFloat && C.dim() == 3 && C.is_contiguous() &&
+                C.size(1) == M && C.size(2) == N, "kgc.w4_dgemm: C fp32 contiguous [S, M, N]");
+    S = C.size(0);
+    ss = C.stride(0);
+    TORCH_CHECK(S >= 1 && S <= 32 && S <= K / 64, "kgc.w4_dgemm: 1 <= S <= min(32, K / 64)");
+    TORCH_CHECK(!bias.has_value(), "kgc.w4_dgemm: no bias on fp32 slices");
+  } else {
+    TORCH_CHECK(epi != 2 || ((N / 2) % 64 == 0 && !bias.has_value()),
+                "kgc.w4_dgemm: silu epilogue needs (N/2) % 64 == 0 and no bias");
+    TORCH_CHECK(C.scalar_type() == X.scalar_type() && C.dim() == 2 && C.is_contiguous() &&
+                C.size(0) == M && C.size(1) == (epi == 2 ? N / 2 : N),
+                "kgc.w4_dgemm: C [M, N] (epi 1) or [M, N/2] (epi 2), contiguous, X's dtype");
+  }
+  TORCH_CHECK((M + bm - 1) / bm * (N / bn) * S < ((int64_t)1 << 31), "kgc.w4_dgemm: grid too large");
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N &&
+                bias->scalar_type() == X.scalar_type(), "kgc.w4_dgemm: bias [N] in X's dtype");
+    check_same_dev(X, *bias, "bias");
+    bp = bias->data_ptr();
+  }
+  kgc::launch_w4_dgemm(dt_code(X), (int)cfg, (int)epi, C.data_ptr(), X.data_ptr(), Wp.data_ptr(),
+                       bp, (int)M, (int)N, (int)K, X.stride(0), (int)S, ss, stream());
+}
+
+// P [N/128, K/64, 4352] <- codes W4 [N, K/2] + scales [N, K/32] re-laid out for K9mf (silu:
+// merged [gate; up])
+void w4_dgemm_pack(Tensor P, Tensor W4, Tensor scales, bool silu) {
+  check_gpu(W4, "W4");
+  check_same_dev(W4, P, "P");
+  check_same_dev(W4, scales, "scales");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(W4.device());
+  TORCH_CHECK(W4.dim() == 2 && W4.is_contiguous() && W4.scalar_type() == at::kByte,
+              "kgc.w4_dgemm_pack: W4 [N, K/2] uint8 contiguous");
+  const int64_t N = W4.size(0), K = 2 * W4.size(1);
+  TORCH_CHECK(N % 128 == 0 && K % 64 == 0 && (!silu || (N / 2) % 64 == 0) &&
+              N * K < ((int64_t)1 << 40), "kgc.w4_dgemm_pack: N % 128, K % 64");
+  TORCH_CHECK(N <= INT32_MAX && K <= INT32_MAX, "kgc.w4_dgemm_pack: dims overflow");
+  TORCH_CHECK(scales.scalar_type() == at::kByte && scales.dim() == 2 && scales.is_contiguous() &&
+              scales.size(0) == N && scales.size(1) == K / 32,
+              "kgc.w4_dgemm_pack: scales [N, K/32] uint8 contiguous");
+  TORCH_CHECK(P.scalar_type() == at::kByte && P.dim() == 3 && P.is_contiguous() &&
+              P.size(0) == N / 128 && P.size(1) == K / 64 && P.size(2) == 128 * 32 + 256,
+              "kgc.w4_dgemm_pack: P [N/128, K/64, 4352] uint8 contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(P.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(W4.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(scales.data_ptr()) % 4 == 0,
+              "kgc.w4_dgemm_pack: alignment");
+  kgc::launch_w4_dgemm_pack(silu, P.data_ptr(), W4.data_ptr(), scales.data_ptr(), (int)N, (int)K,
+                            stream());
+}
+
+int64_t w4_dgemm_num_cfgs() { return kgc::w4_dgemm_num_cfgs(); }
+std::vector<int64_t> w4_dgemm_cfg_info(int64_t cfg) {
+  TORCH_CHECK(cfg >= 0 && cfg < kgc::w4_dgemm_num_cfgs(), "kgc.w4_dgemm: unknown tile config");
+  int bm, bn, ns;
+  kgc::w4_dgemm_cfg_info((int)cfg, &bm, &bn, &ns);
+  return {bm, bn, ns};
+}
+
 void sample_stamps_enable(bool on) { kgc::sample_stamps_enable(on); }
 
 std::vector<int64_t> sample_stamps() {
@@ -1561,6 +1649,10 @@ TORCH_LIBRARY(kgc, m) {
   m.def("w8_dgemm_pack(Tensor(a!) P, Tensor W8, bool silu) -> ()");
   m.def("w8_dgemm_num_cfgs() -> int", &w8_dgemm_num_cfgs);
   m.def("w8_dgemm_cfg_info(int cfg) -> int[]", &w8_dgemm_cfg_info);
+  m.def("w4_dgemm(Tensor(a!) C, Tensor X, Tensor Wp, Tensor? bias, int cfg, int epi) -> ()");
+  m.def("w4_dgemm_pack(Tensor(a!) P, Tensor W4, Tensor scales, bool silu) -> ()");
+  m.def("w4_dgemm_num_cfgs() -> int", &w4_dgemm_num_cfgs);
+  m.def("w4_dgemm_cfg_info(int cfg) -> int[]", &w4_dgemm_cfg_info);
 }
 
 TORCH_LIBRARY_IMPL(kgc, CUDA, m) {
@@ -1604,4 +1696,6 @@ TORCH_LIBRARY_IMPL(kgc, CUDA, m) {
   m.impl("w4_widen", &w4_widen);
   m.impl("w8_dgemm", &w8_dgemm);
   m.impl("w8_dgemm_pack", &w8_dgemm_pack);
+  m.impl("w4_dgemm", &w4_dgemm);
+  m.impl("w4_dgemm_pack", &w4_dgemm_pack);
 }

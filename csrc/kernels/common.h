@@ -142,6 +142,33 @@ __device__ __forceinline__ u32x4 fp8x8_widen(u32x2 raw) {
                fp8x2_widen<T, false>(raw.y), fp8x2_widen<T, true>(raw.y)};
 }
 
+// ---- MXFP4 (OCP e2m1 codes + e8m0 block scales; gemm_w4.hip, gemm_w4_decode.hip)
+// one dword of codes (8 e2m1, k ascending from the low nibble of byte 0) -> 8 T, each
+// multiplied by sc (a power of two: exact)
+template <typename T>
+__device__ __forceinline__ u32x4 fp4x8_widen(uint32_t w, float sc) {
+  if constexpr (std::is_same_v<T, bf16>) {
+    union { bf16x2_t v; uint32_t u; } r0, r1, r2, r3;
+    r0.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 0);
+    r1.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 1);
+    r2.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 2);
+    r3.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 3);
+    return u32x4{r0.u, r1.u, r2.u, r3.u};
+  } else {
+    union { f16x2_t v; uint32_t u; } r0, r1, r2, r3;
+    r0.v = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 0);
+    r1.v = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 1);
+    r2.v = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 2);
+    r3.v = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 3);
+    return u32x4{r0.u, r1.u, r2.u, r3.u};
+  }
+}
+
+// e8m0 byte `sub` of a scale dword -> fp32 2^(b - 127)
+__device__ __forceinline__ float e8m0_f32(uint32_t dw, int sub) {
+  return __builtin_bit_cast(float, ((dw >> (8 * sub)) & 0xffu) << 23);
+}
+
 // Load one 8-element fragment from a cache row: 16 B of T, or 8 B of fp8 widened.
 template <typename T, bool KV8>
 __device__ __forceinline__ u32x4 ld_frag8(const void* base, int64_t elem) {

@@ -48,37 +48,15 @@
 // lanes of batch rows >= M load nothing, and register sets of half the depth (112 VGPRs,
 // 4 waves per SIMD).
 //
-// w4_widen: out[n, k] = dq(W4)[n, k] in bf16 / f16, exact -- prefill and every M > 64 widen a
-// weight into a static scratch and run the library GEMM on it.
+// w4_widen: out[n, k] = dq(W4)[n, k] in bf16 / f16, exact -- prefill, and the M > 64 that K9mf
+// (gemm_w4_decode.hip) does not run, widen a weight into a static scratch and run the library
+// GEMM on it.
 #include "common.h"
 #include "launch.h"
 
 namespace kgc {
 
-// one dword of codes (8 e2m1, k ascending from the low nibble of byte 0) -> 8 T
-template <typename T>
-__device__ __forceinline__ u32x4 fp4x8_widen(uint32_t w, float sc) {
-  if constexpr (std::is_same_v<T, bf16>) {
-    union { bf16x2_t v; uint32_t u; } r0, r1, r2, r3;
-    r0.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 0);
-    r1.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 1);
-    r2.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 2);
-    r3.v = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, sc, 3);
-    return u32x4{r0.u, r1.u, r2.u, r3.u};
-  } else {
-    union { f16x2_t v; uint32_t u; } r0, r1, r2, r3;
-    r0.v = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 0);
-    r1.v = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 1);
-    r2.v = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 2);
-    r3.v = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(w, sc, 3);
-    return u32x4{r0.u, r1.u, r2.u, r3.u};
-  }
-}
-
-// e8m0 byte `sub` of a scale dword -> fp32 2^(b - 127)
-__device__ __forceinline__ float e8m0_f32(uint32_t dw, int sub) {
-  return __builtin_bit_cast(float, ((dw >> (8 * sub)) & 0xffu) << 23);
-}
+// (fp4x8_widen and e8m0_f32 live in common.h: K9mf, gemm_w4_decode.hip, widens the same way)
 
 template <typename T, int MT, int NT, int NW, bool SILU>
 __global__ __launch_bounds__(NW * 64) void w4_gemm_kernel(

@@ -134,6 +134,18 @@ void launch_w4_gemm(int dtype, int mt, int nt, int nw, bool silu, void* C, const
                     int64_t ldx, int64_t ldc, hipStream_t s);
 void launch_w4_widen(int dtype, void* out, const void* W, const void* S, int64_t N, int64_t K,
                      hipStream_t s);
+// K9mf (gemm_w4_decode.hip): the K9m pipeline over packed MXFP4 weights
+// Wp [N/128][K/64][4096 B codes + 256 B scales] (launch_w4_dgemm_pack; silu: gate / up
+// 16-row groups interleaved), 64 < M <= 512.  epi 0: fp32 slice z of C [S, M, N];
+// 1: C [M, N] = acc (+ bias) (S = 1); 2: silu pairs of a SiLU-packed merged [gate; up]
+// weight into C [M, N/2] (S = 1).  w4_dgemm_cfg_info: BM, BN, ring slots.
+int w4_dgemm_num_cfgs();
+void w4_dgemm_cfg_info(int cfg, int* bm, int* bn, int* ns);
+void launch_w4_dgemm(int dtype, int cfg, int epi, void* C, const void* X, const void* Wp,
+                     const void* bias, int M, int N, int K, int64_t ldx, int S,
+                     int64_t slice_stride, hipStream_t s);
+void launch_w4_dgemm_pack(bool silu, void* P, const void* W4, const void* scales, int N, int K,
+                          hipStream_t s);
 
 // K13/K14 MoE: routing, expert bucketing, grouped MFMA GEMM, weighted combine.
 int moe_block_n();

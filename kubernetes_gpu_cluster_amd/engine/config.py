@@ -147,8 +147,9 @@ def add_engine_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
            "weight back to the model dtype before the library GEMM, which moves MORE bytes "
            "than unquantised weights would.  mxfp4: online round-to-nearest OCP MXFP4 "
            "(W4A16, 4.25 bits per weight) of the same linears: a quarter of the weight bytes "
-           "and the K9f GEMM at decode batches <= 64; every larger batch and prefill take "
-           "the widen path; less accurate than fp8.  Not for MoE or OPT models")
+           "and the K9f GEMM at decode batches <= 64, the K9mf GEMM over packed copies at "
+           "decode batches 65-512 (KGC_W4_DGEMM=0: none); prefill takes the widen path; "
+           "less accurate than fp8.  Not for MoE or OPT models")
     a("--seed", type=int, default=0)
     a("--random-init", action="store_true", help="random weights (offline benchmarking)")
     a("--load-format", type=str, default="auto", help="'dummy' == --random-init")

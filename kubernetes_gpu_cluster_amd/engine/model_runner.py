@@ -727,13 +727,14 @@ class ModelRunner:
                              self.buckets, self.dtype, silu_shapes=gu,
                              tail_shapes=getattr(self.model, "w8_tail_shapes", lambda: set())())
             elif method == "mxfp4":
-                # --quantization mxfp4: K9f's configurations (M <= 64) against the widen
-                # path, per bucket; the stored weight is [N, K/2] bytes
+                # --quantization mxfp4: K9f's (M <= 64) and K9mf's (M > 64) configurations
+                # against the widen path, per bucket; the stored weight is [N, K/2] bytes
                 from ..models.quant import dense_projections
                 gu = {(l.mlp.gate_up_proj.weight.shape[0], 2 * l.mlp.gate_up_proj.weight.shape[1])
                       for l in self.model.layers}
                 gemm.tune_w4([m.weight for l in self.model.layers for m in dense_projections(l)],
-                             self.buckets, self.dtype, silu_shapes=gu)
+                             self.buckets, self.dtype, silu_shapes=gu,
+                             tail_shapes=getattr(self.model, "w4_tail_shapes", lambda: set())())
         whole = self.model.first and self.model.last
         if (not self.use_graphs or not (whole or self.pp_link is not None)
                 or not getattr(self.model, "graph_safe", True)):

@@ -132,19 +132,21 @@ class Worker:
             # (models/quant.py)
             from ..models.quant import quantize_model
             quantize_model(self.model, cfg.quantization)
-            if cfg.quantization == "fp8" and dev.type == "cuda" and cfg.cuda_graph_max_bs > 64:
-                # packed e4m3 copies for K9mq at the decode buckets above 64 rows, eager and
-                # graph engines alike (the same kernels); they come out of the KV pool sized
-                # below (KGC_W8_DGEMM=0: none)
+            if dev.type == "cuda" and cfg.cuda_graph_max_bs > 64:
+                # packed copies (e4m3 tiles for K9mq, mxfp4 tiles for K9mf) at the decode
+                # buckets above 64 rows, eager and graph engines alike (the same kernels);
+                # they come out of the KV pool sized below (KGC_W8_DGEMM=0 / KGC_W4_DGEMM=0:
+                # none)
                 from ..models.quant import dense_projections
                 from ..ops import gemm
                 gu = [l.mlp.gate_up_proj.weight for l in self.model.layers]
                 skip = {id(w) for w in gu}
-                nb = gemm.pack_w8_decode_weights(
-                    [m.weight for l in self.model.layers for m in dense_projections(l)
-                     if id(m.weight) not in skip], gu)
-                log.info("quantization %s: %.2f GB of packed K9mq weight copies", cfg.quantization,
-                         nb / 1e9)
+                pack, kname = ((gemm.pack_w8_decode_weights, "K9mq") if cfg.quantization == "fp8"
+                               else (gemm.pack_w4_decode_weights, "K9mf"))
+                nb = pack([m.weight for l in self.model.layers for m in dense_projections(l)
+                           if id(m.weight) not in skip], gu)
+                log.info("quantization %s: %.2f GB (%d bytes) of packed %s weight copies",
+                         cfg.quantization, nb / 1e9, nb, kname)
         if dev.type == "cuda" and not cfg.enforce_eager:
             # packed copies of the decode-GEMM weights for the K9m tiles, made before the
             # KV cache is sized so the pool accounts for them (ops/gemm.py)

@@ -118,9 +118,11 @@ _plan_w8_dg: dict[tuple[int, int, int, str], Optional[tuple[int, int]]] = {}
 # KGC_W8_DGEMM: "1" tuned (default), "0" off (nothing packed, the widen path runs), "force"
 # (no timing: the first configuration in table order that fits, S = 1 -- tests, A/B runs)
 w8_dgemm_mode = os.environ.get("KGC_W8_DGEMM", "1")
-# packed e4m3 copies for K9mq: (data_ptr, silu) -> (weakref to the fp8 weight, packed tiles,
-# silu: the row scales in the packed tiles' row order, for the split-K slices)
-_w8_packed: dict[tuple[int, bool], tuple] = {}
+# packed copies of quantised weights (K9mq's e4m3 tiles, K9mf's mxfp4 tiles): (data_ptr, silu)
+# -> (weakref to the weight, packed tiles, extra); extra, fp8 silu only: the row scales in
+# the packed tiles' row order, for the split-K slices.  The weakref drops the entry when the
+# weight dies, as in _packed
+_q_packed: dict[tuple[int, bool], tuple] = {}
 # K9q configurations: K9's, except (4, 2, 16), which does not fit 128 VGPRs per lane
 _W8_CONFIGS = [c for c in _CONFIGS if c[:3] != (4, 2, 16)]
 
@@ -263,13 +265,22 @@ def w8_counts() -> dict:
 #            or no K9f configuration fits the shape -- the widen path;
 #   M  > 64, prefill: the widen path: kgc.w4_widen writes the exact dequantised weight into
 #            the static scratch fp8 uses (one per device and dtype) and the library GEMM
-#            runs on it.  It moves more bytes than a bf16 weight would.
+#            runs on it.  It moves more bytes than a bf16 weight would -- except at the
+#            decode buckets with 64 < M <= 512 where the plan below names a K9mf
+#            configuration (csrc/kernels/gemm_w4_decode.hip: the K9m pipeline streaming
+#            packed mxfp4 tiles, 0.53 bytes per weight element).
 # (M, N, K) -> K9f cfg (mt, nt, nw), or None where the widen path measured faster
 _plan_w4: dict[tuple[int, int, int], Optional[tuple]] = {}
 # merged gate_up (M, 2I, K) -> cfg of K9f's SiLU form, where it beat the plan + silu_mul
 _plan_w4_silu: dict[tuple[int, int, int], Optional[tuple]] = {}
-_w4_counts = {"k9f": 0, "k9f_silu": 0, "widen": 0}
+_w4_counts = {"k9f": 0, "k9f_silu": 0, "widen": 0, "k9mf": 0, "k9mf_silu": 0}
 _w4_enabled = os.environ.get("KGC_W4_GEMM", "1") != "0"
+# K9mf: (M, N, K, kind) -> (cfg, S), or None where the widen path (with the same consumer)
+# measured faster; kind as in _plan_dg ("plain" | "silu" | "tail").  No entry: widen.
+_plan_w4_dg: dict[tuple[int, int, int, str], Optional[tuple[int, int]]] = {}
+# KGC_W4_DGEMM: "1" tuned (default), "0" off (nothing packed, the widen path runs), "force"
+# (no timing: the first configuration in table order that fits, S = 1 -- tests, A/B runs)
+w4_dgemm_mode = os.environ.get("KGC_W4_DGEMM", "1")
 _U8 = torch.uint8
 # K9f configurations (mt, nt, nw); (4, 2, 8) is not built (64 KB of LDS partial sums)
 _W4_CONFIGS = [(mt, nt, nw) for mt in (1, 2, 4) for nt in (1, 2) for nw in (2, 4, 8)
@@ -351,6 +362,15 @@ def w4_linear(x: torch.Tensor, w4: torch.Tensor, bias: Optional[torch.Tensor] = 
         cfg = _plan_w4[key] if key in _plan_w4 else w4_default_cfg(M, N, K)
         if cfg is not None:
             return w4_gemm(x, w4, scales, bias, cfg)
+    p = _w4_dg_plan(x, w4, "plain")
+    if p is not None and (p[1] == 1 or bias is None):
+        cfg, S = p
+        if S == 1:
+            return w4_dgemm(x, w4, cfg, 1, bias=bias)
+        from . import _k
+        out = torch.empty(M, N, dtype=x.dtype, device=x.device)
+        _k().splitk_reduce(out, w4_dgemm(x, w4, cfg, S))
+        return out
     return w4_widen_linear(x, w4, scales, bias)
 
 
@@ -363,6 +383,15 @@ def w4_linear_silu(x: torch.Tensor, w4: torch.Tensor, bias: Optional[torch.Tenso
         cfg = _plan_w4_silu[key] if key in _plan_w4_silu else w4_default_cfg(*key, silu=True)
         if cfg is not None:
             return w4_silu(x, w4, w4_scale(w4), cfg)
+    p = _w4_dg_plan(x, w4, "silu") if bias is None and x.is_cuda else None
+    if p is not None:
+        cfg, S = p
+        if S == 1:
+            return w4_dgemm(x, w4, cfg, 1, epi=2)
+        from . import _k
+        out = torch.empty(x.shape[0], w4.shape[0] // 2, dtype=x.dtype, device=x.device)
+        _k().splitk_reduce_silu(out, w4_dgemm(x, w4, cfg, S, silu_w=True), True)
+        return out
     return silu_mul(w4_linear(x, w4, bias))
 
 
@@ -381,13 +410,17 @@ def w4_counts() -> dict:
 
 @torch.inference_mode()
 def tune_w4(weights: Iterable[torch.Tensor], ms: Iterable[int], dtype: torch.dtype,
-            silu_shapes=(), reps: int = 3) -> dict:
+            silu_shapes=(), reps: int = 3, tail_shapes=()) -> dict:
     """For each mxfp4 weight shape and decode bucket M <= 64: every K9f configuration against
     the widen path, graph-replayed over ALL weights of the shape (HBM-resident, as in a
     decode step); the faster goes into the W4 plan.  ``silu_shapes``: (N, K) of merged
-    gate_up weights, whose SiLU form is timed against the plain winner + silu_mul.  Buckets
-    above 64 have no mxfp4 kernel yet: they take the widen path without a plan entry.
-    Returns {(M, N, K): (chosen cfg or None, widen us, best K9f us, best K9f cfg)}."""
+    gate_up weights, whose SiLU form is timed against the plain winner + silu_mul.
+    Decode buckets with 64 < M <= 512: the K9mf candidates against the widen path, each
+    with its consumer (``_tune_w4_dgemm``; ``tail_shapes``: (N, K) of the o / down
+    projections that feed ``linear_add_rms``), only for the weights
+    ``pack_w4_decode_weights`` packed -- the results go into ``w4_dg_plan()``, never into
+    ``w4_plan()``.  Returns {(M, N, K): (chosen cfg or None, widen us, best K9f us, best K9f
+    cfg)} and the same under (M, N, K, kind) for K9mf."""
     from . import silu_mul
     from .quant import is_mxfp4, w4_scale
     if not _w4_enabled:
@@ -397,7 +430,13 @@ def tune_w4(weights: Iterable[torch.Tensor], ms: Iterable[int], dtype: torch.dty
         if w.is_cuda and w.dim() == 2 and is_mxfp4(w):
             by_shape.setdefault((w.shape[0], 2 * w.shape[1]), []).append(w)
     res = {}
+    ms = list(ms)
     for (N, K), ws in sorted(by_shape.items()):
+        if w4_dgemm_mode != "0":
+            kind = ("silu" if (N, K) in silu_shapes else
+                    "tail" if (N, K) in tail_shapes else "plain")
+            _tune_w4_dgemm(ws, N, K, [m for m in ms if SKINNY_MAX_M < m <= DG_MAX_M], dtype,
+                           reps, res, kind)
         sc = [w4_scale(w) for w in ws]
         n = len(ws)
         for M in sorted(set(m for m in ms if 1 <= m <= SKINNY_MAX_M)):
@@ -474,42 +513,48 @@ def w8_dg_plan() -> dict:
     return dict(_plan_w8_dg)
 
 
-def _w8_packed_entry(w8: torch.Tensor, silu: bool) -> Optional[tuple]:
-    key = (w8.data_ptr(), silu)
-    e = _w8_packed.get(key)
+def _q_packed_entry(w: torch.Tensor, silu: bool) -> Optional[tuple]:
+    """The registry entry (weakref, packed tiles, extra) of a quantised weight's packed copy
+    (K9mq's e4m3 tiles or K9mf's mxfp4 tiles), or None."""
+    key = (w.data_ptr(), silu)
+    e = _q_packed.get(key)
     if e is None:
         return None
     src = e[0]()
     if src is None:
-        _w8_packed.pop(key, None)
+        _q_packed.pop(key, None)
         return None
-    if src.data_ptr() != w8.data_ptr() or src.shape != w8.shape:
+    if src.data_ptr() != w.data_ptr() or src.shape != w.shape or src.dtype != w.dtype:
         return None
     return e
 
 
-def _w8_packed_get(w8: torch.Tensor, silu: bool) -> Optional[torch.Tensor]:
-    e = _w8_packed_entry(w8, silu)
+def _q_packed_get(w: torch.Tensor, silu: bool) -> Optional[torch.Tensor]:
+    e = _q_packed_entry(w, silu)
     return None if e is None else e[1]
+
+
+def _q_packed_put(w: torch.Tensor, silu: bool, p: torch.Tensor, extra=None) -> None:
+    key = (w.data_ptr(), silu)
+
+    def drop(ref, key=key):
+        e = _q_packed.get(key)
+        if e is not None and e[0] is ref:
+            del _q_packed[key]
+    _q_packed[key] = (weakref.ref(w, drop), p, extra)
 
 
 def _w8_packed_put(w8: torch.Tensor, silu: bool, p: torch.Tensor) -> None:
     from .quant import tile_rows, w8_scale
-    key = (w8.data_ptr(), silu)
     # the SiLU-packed tiles' columns are gate / up groups interleaved: a slice's column c
     # is weight row tile_rows[c], so the slices take the scales in that order
     sc = w8_scale(w8)[tile_rows(w8.shape[0], True, w8.device).flatten()].contiguous() if silu \
         else None
-
-    def drop(ref, key=key):
-        e = _w8_packed.get(key)
-        if e is not None and e[0] is ref:
-            del _w8_packed[key]
-    _w8_packed[key] = (weakref.ref(w8, drop), p, sc)
+    _q_packed_put(w8, silu, p, sc)
 
 
 def w8_packed_weight(w8: torch.Tensor, silu: bool = False) -> Optional[torch.Tensor]:
-    return _w8_packed_get(w8, silu)
+    return _q_packed_get(w8, silu)
 
 
 def pack_w8_decode_weights(plain: Iterable[torch.Tensor], silu: Iterable[torch.Tensor]) -> int:
@@ -525,7 +570,7 @@ def pack_w8_decode_weights(plain: Iterable[torch.Tensor], silu: Iterable[torch.T
     for w, sl in [(w, False) for w in plain] + [(w, True) for w in silu]:
         if (w.is_cuda and w.dim() == 2 and w.dtype == _FP8 and w.is_contiguous()
                 and w.shape[0] % 128 == 0 and w.shape[1] % 64 == 0
-                and (not sl or (w.shape[0] // 2) % 64 == 0) and _w8_packed_get(w, sl) is None):
+                and (not sl or (w.shape[0] // 2) % 64 == 0) and _q_packed_get(w, sl) is None):
             todo.append((w, sl))
     need = sum(w.numel() for w, _ in todo)
     if not todo:
@@ -555,7 +600,7 @@ def w8_dgemm(x: torch.Tensor, w8: torch.Tensor, cfg: int, S: int, epi: int = 1,
     from . import _k
     from .quant import w8_scale
     silu = epi == 2 or silu_w
-    e = _w8_packed_entry(w8, silu)
+    e = _q_packed_entry(w8, silu)
     if e is None:
         raise RuntimeError("K9mq: the weight has no packed copy (pack_w8_decode_weights)")
     wp = e[1]
@@ -579,13 +624,14 @@ def _w8_dg_plan(x: torch.Tensor, w8: torch.Tensor, kind: str):
     if not _plan_w8_dg or w8_dgemm_mode == "0" or not x.is_cuda or not _w8_x_ok(x):
         return None
     p = _plan_w8_dg.get((x.shape[0], w8.shape[0], w8.shape[1], kind))
-    if p is None or _w8_packed_get(w8, kind == "silu") is None:
+    if p is None or _q_packed_get(w8, kind == "silu") is None:
         return None
     return p
 
 
-def _w8_dg_candidates(M: int, N: int, K: int, kind: str):
-    tiles = _w8_dg_tiles()
+def _q_dg_candidates(M: int, N: int, K: int, tiles: list):
+    """(cfg, S) candidates of a quantised K9m-pipeline kernel (K9mq, K9mf) with the tile
+    table ``tiles``."""
     out = []
     for c, (bm, bn, _) in enumerate(tiles):
         # 128-row blocks up to M = 128, 256-row blocks above (K9m's split)
@@ -599,28 +645,26 @@ def _w8_dg_candidates(M: int, N: int, K: int, kind: str):
     return out
 
 
-def _tune_w8_dgemm(ws, N: int, K: int, ms, dtype, reps: int, res: dict, kind: str) -> None:
-    """The widen path vs the K9mq candidates at each M in ``ms``, over all weights of the
-    shape, each side timed WITH its consumer ("silu": SiLU-and-mul, "tail": residual add +
-    RMSNorm, "plain": the split-K reduction) on graph replays; an entry is made only where
-    K9mq measured faster (None otherwise).  KGC_W8_DGEMM=force: no timing."""
+def _tune_q_dgemm(n: int, dev, N: int, K: int, ms, dtype, reps: int, res: dict, kind: str, *,
+                  tag: str, kname: str, mode: str, plan: dict, tiles: list, wide_linear,
+                  launch) -> None:
+    """The widen path vs the (cfg, S) candidates of a quantised K9m-pipeline kernel (K9mq,
+    K9mf) at each M in ``ms``, over the ``n`` weights of the shape, each side timed WITH its
+    consumer ("silu": SiLU-and-mul, "tail": residual add + RMSNorm, "plain": the split-K
+    reduction) on graph replays; ``plan`` gets the winner where the kernel measured faster
+    (None otherwise).  ``wide_linear(x, i)``: the widen path on weight i;
+    ``launch(buf, x, i, cfg, epi)``: the kernel on weight i's packed copy.  mode "force": no
+    timing, the first configuration in table order that fits, S = 1."""
     from . import _k, fused_add_rms_norm, silu_mul
-    from .quant import w8_scale
     silu = kind == "silu"
-    if any(_w8_packed_get(w, silu) is None for w in ws):
-        return
-    dev = ws[0].device
-    sc = [w8_scale(w) for w in ws]
-    wps = [_w8_packed_get(w, silu) for w in ws]
-    sc_il = [_w8_packed_entry(w, silu)[2] for w in ws]      # silu slices: tile row order
     for M in sorted(set(ms)):
         if not w8_dg_ok(M, N, K) or (kind == "tail" and N > 8192):
             continue
         key = (M, N, K, kind)
-        if w8_dgemm_mode == "force":
-            first = next((c for c in range(len(_w8_dg_tiles())) if w8_dg_ok(M, N, K, c, 1)), None)
+        if mode == "force":
+            first = next((c for c in range(len(tiles)) if w8_dg_ok(M, N, K, c, 1)), None)
             if first is not None:
-                _plan_w8_dg[key] = (first, 1)
+                plan[key] = (first, 1)
                 res[key] = ((first, 1), float("nan"), float("nan"), (first, 1))
             continue
         x = torch.randn(M, K, dtype=dtype, device=dev)
@@ -630,25 +674,25 @@ def _tune_w8_dgemm(ws, N: int, K: int, ms, dtype, reps: int, res: dict, kind: st
         red = torch.empty(M, No, dtype=dtype, device=dev)
 
         def wide():
-            for w, s in zip(ws, sc):
-                y = w8_widen_linear(x, w, s)
+            for i in range(n):
+                y = wide_linear(x, i)
                 if silu:
                     silu_mul(y, red)
                 elif kind == "tail":
                     fused_add_rms_norm(y, res_t, gamma, 1e-6)
         timed = []
-        for cfg, S in _w8_dg_candidates(M, N, K, kind):
+        for cfg, S in _q_dg_candidates(M, N, K, tiles):
             buf = (torch.empty(S, M, N, dtype=torch.float32, device=dev) if S > 1 else
                    torch.empty(M, No, dtype=dtype, device=dev))
 
             def run(cfg=cfg, S=S, buf=buf):
-                for wp, s in zip(wps, sc_il if silu and S > 1 else sc):
+                for i in range(n):
                     if S == 1:
-                        _k().w8_dgemm(buf, x, wp, s, None, cfg, 2 if silu else 1)
+                        launch(buf, x, i, cfg, 2 if silu else 1)
                         if kind == "tail":
                             fused_add_rms_norm(buf, res_t, gamma, 1e-6)
                     else:
-                        _k().w8_dgemm(buf, x, wp, s, None, cfg, 0)
+                        launch(buf, x, i, cfg, 0)
                         if silu:
                             _k().splitk_reduce_silu(red, buf, True)
                         elif kind == "tail":
@@ -674,13 +718,146 @@ def _tune_w8_dgemm(ws, N: int, K: int, ms, dtype, reps: int, res: dict, kind: st
         med = {c: sorted(v)[len(v) // 2] for c, v in rounds.items()}
         best = min(med, key=med.get)
         best_t, wide_t = med[best], sorted(wide_r)[len(wide_r) // 2]
-        n = len(ws)
         chosen = best if best_t < wide_t else None
-        _plan_w8_dg[key] = chosen
+        plan[key] = chosen
         res[key] = (chosen, wide_t * 1e3 / n, best_t * 1e3 / n, best)
-        log.info("gemm W8 M=%d N=%d K=%d %s: widen + hipBLASLt %.1f us, K9mq %s %.1f us -> %s",
-                 M, N, K, kind, wide_t * 1e3 / n, best, best_t * 1e3 / n,
-                 "K9mq" if chosen else "widen")
+        log.info("gemm %s M=%d N=%d K=%d %s: widen + hipBLASLt %.1f us, %s %s %.1f us -> %s",
+                 tag, M, N, K, kind, wide_t * 1e3 / n, kname, best, best_t * 1e3 / n,
+                 kname if chosen else "widen")
+
+
+def _tune_w8_dgemm(ws, N: int, K: int, ms, dtype, reps: int, res: dict, kind: str) -> None:
+    """``_tune_q_dgemm`` for K9mq over the fp8 weights ``ws`` of one shape (all packed, or
+    nothing is tuned).  KGC_W8_DGEMM=force: no timing."""
+    from . import _k
+    from .quant import w8_scale
+    silu = kind == "silu"
+    if any(_q_packed_get(w, silu) is None for w in ws):
+        return
+    sc = [w8_scale(w) for w in ws]
+    wps = [_q_packed_get(w, silu) for w in ws]
+    sc_il = [_q_packed_entry(w, silu)[2] for w in ws]      # silu slices: tile row order
+
+    def launch(buf, x, i, cfg, epi):
+        _k().w8_dgemm(buf, x, wps[i], (sc_il if silu and epi == 0 else sc)[i], None, cfg, epi)
+    _tune_q_dgemm(len(ws), ws[0].device, N, K, ms, dtype, reps, res, kind, tag="W8",
+                  kname="K9mq", mode=w8_dgemm_mode, plan=_plan_w8_dg, tiles=_w8_dg_tiles(),
+                  wide_linear=lambda x, i: w8_widen_linear(x, ws[i], sc[i]), launch=launch)
+
+
+# ------------------------------------------------------------------ K9mf (64 < M <= 512)
+_W4_DG_TILES: list = []          # (BM, BN, ring slots) per configuration id, read once
+
+
+def _w4_dg_tiles() -> list:
+    if not _W4_DG_TILES:
+        from . import _k
+        _W4_DG_TILES.extend(tuple(int(v) for v in _k().w4_dgemm_cfg_info(c))
+                            for c in range(int(_k().w4_dgemm_num_cfgs())))
+    return _W4_DG_TILES
+
+
+def w4_dg_ok(M: int, N: int, K: int, cfg: int = 0, S: int = 1) -> bool:
+    """Shapes K9mf takes (K the layer's, not the code bytes): K9mq's -- 64 < M <= 512, N in
+    whole 128-column tiles, K in whole 64-k steps, at most one K-slice per step (and the 32
+    slices the binding allows)."""
+    return w8_dg_ok(M, N, K, cfg, S)
+
+
+def w4_dg_plan() -> dict:
+    return dict(_plan_w4_dg)
+
+
+def w4_packed_weight(w4: torch.Tensor, silu: bool = False) -> Optional[torch.Tensor]:
+    return _q_packed_get(w4, silu)
+
+
+def pack_w4_decode_weights(plain: Iterable[torch.Tensor], silu: Iterable[torch.Tensor]) -> int:
+    """Packed copies ([N/128][K/64][4096 B codes + 256 B scales] tiles,
+    ``quant.pack_mxfp4_tiles_reference``) of an mxfp4 model's decode-GEMM weights for K9mf,
+    made once before the KV cache is sized.  ``silu``: merged gate_up weights, packed with
+    gate and up 16-row groups interleaved.  Nothing is packed (the widen path stays) with
+    KGC_W4_DGEMM=0 or when the copies would exceed KGC_DGEMM_PACK_FRACTION of device memory.
+    Returns bytes packed."""
+    if w4_dgemm_mode == "0" or not _w4_enabled:
+        return 0
+    from . import _k
+    from .quant import MXFP4_TILE_BYTES, is_mxfp4, w4_scale
+    todo = []
+    for w, sl in [(w, False) for w in plain] + [(w, True) for w in silu]:
+        if (w.is_cuda and w.dim() == 2 and is_mxfp4(w) and w.is_contiguous()
+                and w.shape[0] % 128 == 0 and w.shape[1] % 32 == 0
+                and (not sl or (w.shape[0] // 2) % 64 == 0) and _q_packed_get(w, sl) is None):
+            todo.append((w, sl))
+    need = sum(w.shape[0] // 128 * (w.shape[1] // 32) * MXFP4_TILE_BYTES for w, _ in todo)
+    if not todo:
+        return 0
+    free, total = torch.cuda.mem_get_info(todo[0][0].device)
+    if need > _PACK_FRACTION * total or need > free - (8 << 30):
+        log.info("K9mf: %.1f GB of packed mxfp4 weights exceeds the budget; widen path only",
+                 need / 1e9)
+        return 0
+    for w, sl in todo:
+        p = torch.empty(w.shape[0] // 128, w.shape[1] // 32, MXFP4_TILE_BYTES, dtype=_U8,
+                        device=w.device)
+        _k().w4_dgemm_pack(p, w.detach(), w4_scale(w), sl)
+        _q_packed_put(w, sl, p)
+    log.info("K9mf: packed %d mxfp4 decode weights (%.2f GB, out of the KV pool; "
+             "KGC_W4_DGEMM=0 returns them)", len(todo), need / 1e9)
+    return need
+
+
+def w4_dgemm(x: torch.Tensor, w4: torch.Tensor, cfg: int, S: int, epi: int = 1,
+             out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+             silu_w: bool = False) -> torch.Tensor:
+    """K9mf over ``w4``'s packed copy: S == 1 -> x dq(W4)^T (+ bias) in x's dtype (epi 1) or
+    the SiLU pairs [M, N/2] of a merged gate_up weight (epi 2); S > 1 -> the [S, M, N] fp32
+    K-slices (the caller's consumer sums them).  silu_w: slices of the SiLU-packed copy
+    (``splitk_reduce_silu(interleaved=True)``)."""
+    from . import _k
+    silu = epi == 2 or silu_w
+    wp = _q_packed_get(w4, silu)
+    if wp is None:
+        raise RuntimeError("K9mf: the weight has no packed copy (pack_w4_decode_weights)")
+    M, N = x.shape[0], w4.shape[0]
+    if S > 1:
+        if bias is not None:
+            raise RuntimeError("K9mf: no bias on split-K slices")
+        out = torch.empty(S, M, N, dtype=torch.float32, device=x.device) if out is None else out
+        _k().w4_dgemm(out, x, wp, None, cfg, 0)
+    else:
+        if out is None:
+            out = torch.empty(M, N // 2 if epi == 2 else N, dtype=x.dtype, device=x.device)
+        _k().w4_dgemm(out, x, wp, bias, cfg, epi)
+    _w4_counts["k9mf_silu" if silu else "k9mf"] += 1
+    return out
+
+
+def _w4_dg_plan(x: torch.Tensor, w4: torch.Tensor, kind: str):
+    """The K9mf (cfg, S) of this call, or None: no entry, a None entry, the knob off, an X
+    the kernel does not take, or a weight without its packed copy -> the widen path."""
+    if not _plan_w4_dg or w4_dgemm_mode == "0" or not x.is_cuda or not _w8_x_ok(x):
+        return None
+    p = _plan_w4_dg.get((x.shape[0], w4.shape[0], 2 * w4.shape[1], kind))
+    if p is None or _q_packed_get(w4, kind == "silu") is None:
+        return None
+    return p
+
+
+def _tune_w4_dgemm(ws, N: int, K: int, ms, dtype, reps: int, res: dict, kind: str) -> None:
+    """``_tune_q_dgemm`` for K9mf over the mxfp4 weights ``ws`` of one shape (all packed, or
+    nothing is tuned: the tuner never packs).  KGC_W4_DGEMM=force: no timing."""
+    from . import _k
+    from .quant import w4_scale
+    silu = kind == "silu"
+    if any(_q_packed_get(w, silu) is None for w in ws):
+        return
+    sc = [w4_scale(w) for w in ws]
+    wps = [_q_packed_get(w, silu) for w in ws]
+    _tune_q_dgemm(len(ws), ws[0].device, N, K, ms, dtype, reps, res, kind, tag="W4",
+                  kname="K9mf", mode=w4_dgemm_mode, plan=_plan_w4_dg, tiles=_w4_dg_tiles(),
+                  wide_linear=lambda x, i: w4_widen_linear(x, ws[i], sc[i]),
+                  launch=lambda buf, x, i, cfg, epi: _k().w4_dgemm(buf, x, wps[i], None, cfg, epi))
 
 
 @torch.inference_mode()
@@ -911,6 +1088,14 @@ def linear_add_rms(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor,
             return fused_add_rms_norm(w8_dgemm(x, w, cfg, 1), residual, gamma, eps)
         return fused_add_rms_norm(w8_linear(x, w), residual, gamma, eps)
     if w.dtype == _U8:
+        p = _w4_dg_plan(x, w, "tail") if x.is_cuda else None
+        if p is not None and w.shape[0] <= 8192 and residual.is_contiguous():
+            cfg, S = p
+            if S > 1:
+                out = torch.empty_like(residual)
+                _k().splitk_add_rms_norm(out, w4_dgemm(x, w, cfg, S), residual, gamma, eps)
+                return out, residual
+            return fused_add_rms_norm(w4_dgemm(x, w, cfg, 1), residual, gamma, eps)
         return fused_add_rms_norm(w4_linear(x, w), residual, gamma, eps)
     if _plan_accnorm and x.is_cuda and x.dim() == 2 and x.stride(1) == 1:
         cfg = _plan_accnorm.get((x.shape[0], w.shape[0], w.shape[1]))
@@ -1199,6 +1384,7 @@ def save_dg_table(path: str, res: dict, meta: dict) -> int:
 
 def clear_plan() -> None:
     _plan_w8_dg.clear()
+    _plan_w4_dg.clear()
     _plan_w8.clear()
     _plan_w8_silu.clear()
     _plan_w4.clear()
@@ -1236,7 +1422,9 @@ def tail_plan_has_m(M: int) -> bool:
     """A fused projection-tail plan at this M: K9m split-K (M > 64) or SK_ACC_NORM."""
     return (dgemm_plan_has_m(M, "tail") or any(k[0] == M for k in _plan_accnorm)
             or any(k[0] == M and k[3] == "tail" and v is not None
-                   for k, v in _plan_w8_dg.items()))
+                   for k, v in _plan_w8_dg.items())
+            or any(k[0] == M and k[3] == "tail" and v is not None
+                   for k, v in _plan_w4_dg.items()))
 
 
 def accnorm_plan() -> dict:

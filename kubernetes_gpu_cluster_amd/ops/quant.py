@@ -158,6 +158,41 @@ def w4_scale(w4: torch.Tensor) -> torch.Tensor:
     return s
 
 
+MXFP4_TILE_BYTES = 128 * 32 + 256      # a K9mf tile: 128 rows x 64 k of codes + their scales
+
+
+def pack_mxfp4_tiles_reference(codes: torch.Tensor, scales: torch.Tensor,
+                               silu: bool = False) -> torch.Tensor:
+    """The packed layout K9mf (csrc/kernels/gemm_w4_decode.hip) streams, in plain torch on
+    the codes' device: uint8 [N/128, K/64, 4352], one tile per (column tile nb, 64-k step kb)
+    of codes [N, K/2] and scales [N, K/32].  Tile row r holds weight row ``tile_rows(N,
+    silu)[nb, r]`` (as K9mq's tiles: ``silu`` interleaves 16-row groups of gate and up).
+    Bytes [0, 4096): 32-byte code rows of four 8-byte chunks; the chunk at position p of tile
+    row r is k-chunk q = p ^ (2 * ((r // 8) % 2)): code bytes ``32 kb + 4 q + [0, 4)`` of the
+    weight row (k = 64 kb + 8 q + [0, 8)) followed by bytes ``32 kb + 16 + 4 q + [0, 4)``
+    (k = 64 kb + 32 + 8 q + [0, 8)) -- the two MFMA k-halves one lane feeds; the XOR makes
+    the LDS reads conflict-free.  Bytes [4096, 4352): the step's scales as
+    [wn 2][r16 16][n 4][ks 2]: byte ``128 wn + 8 r16 + 2 n + ks`` is scale ``2 kb + ks`` of
+    tile row ``64 wn + 16 n + r16``."""
+    assert codes.dim() == 2 and codes.dtype == torch.uint8 and scales.dtype == torch.uint8
+    N, K = codes.shape[0], 2 * codes.shape[1]
+    assert scales.shape == (N, K // MXFP4_BLOCK)
+    assert N % 128 == 0 and K % 64 == 0 and (not silu or (N // 2) % 64 == 0)
+    dev = codes.device
+    nb, nk = N // 128, K // 64
+    r = torch.arange(128, device=dev)
+    rows = tile_rows(N, silu, dev)
+    t = codes.contiguous()[rows]                              # [nb, r, K/2]
+    t = t.view(nb, 128, nk, 2, 4, 4)                          # [nb, r, kb, half, q, e]
+    t = t.permute(0, 2, 1, 4, 3, 5)                           # [nb, kb, r, q, half, e]
+    q = torch.arange(4, device=dev)[None, :] ^ (2 * ((r // 8) % 2))[:, None]
+    c = t[:, :, r[:, None], q].reshape(nb, nk, 4096)          # [nb, kb, r, position, half, e]
+    s = scales.contiguous()[rows]                             # [nb, r, K/32]
+    s = s.view(nb, 2, 4, 16, nk, 2)                           # [nb, wn, n, r16, kb, ks]
+    s = s.permute(0, 4, 1, 3, 2, 5).reshape(nb, nk, 256)      # [nb, kb, wn, r16, n, ks]
+    return torch.cat([c, s], dim=2).contiguous()
+
+
 def dequantize_mxfp4(codes: torch.Tensor, scales: torch.Tensor,
                      dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """[N, K] ``dtype`` from codes [N, K/2] and scales [N, K/32], in plain torch: the CPU

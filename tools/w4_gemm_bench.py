@@ -1,7 +1,8 @@
 """W4A16 (--quantization mxfp4) GEMMs vs the fp8 and bf16 paths on a model's projection shapes.
 
     python tools/w4_gemm_bench.py [--model llama-3-8b] [--layers 32] [--ms 1,4,16,64]
-                                  [--big-ms 128,256] [--out profiles/w4_gemm_vs_fp8.jsonl]
+                                  [--big-ms 128,256] [--mid-ms 128,256,512]
+                                  [--out profiles/w4_gemm_vs_fp8.jsonl]
 
 Every shape is timed over ``--layers`` distinct weight copies on graph replays (as in a
 decode step the weights stream from HBM, not the 256 MB Infinity Cache), all three sides back
@@ -9,7 +10,10 @@ to back in one process.  One JSON line per case:
   M <= 64: K9f's best configuration and the mxfp4 widen path, K9q's best configuration
            measured TWICE (the spread of the two is the noise of the comparison), and the
            bf16 side as the start-up tuner picks it (K9 skinny or hipBLASLt);
-  --big-ms (M > 64): the mxfp4 widen + hipBLASLt path against plain bf16 hipBLASLt.
+  --big-ms (M > 64): the mxfp4 widen + hipBLASLt path against plain bf16 hipBLASLt;
+  --mid-ms (64 < M <= 512): K9mf per (cfg, S), with the split-K reduction (gate_up: the SiLU
+           epilogue or reduction) in the timing, against widen + hipBLASLt (+ silu_mul), bf16
+           hipBLASLt, and K9mq's best (cfg, S) on the same shape, over ``--big-layers`` weights.
 """
 import argparse
 import json
@@ -29,9 +33,11 @@ def main():
     ap.add_argument("--ms", default="1,4,16,64")
     ap.add_argument("--big-ms", default="")
     ap.add_argument("--big-layers", type=int, default=8)
+    ap.add_argument("--mid-ms", default="")
     ap.add_argument("--gemms", default="qkv,o,gate_up,down")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    from kubernetes_gpu_cluster_amd import ops
     from kubernetes_gpu_cluster_amd.models import configs
     from kubernetes_gpu_cluster_amd.ops import gemm
     from kubernetes_gpu_cluster_amd.ops.quant import quantize_fp8_rows, quantize_mxfp4
@@ -97,6 +103,60 @@ def main():
             emit({"gemm": name, "M": M, "N": N, "K": K, "bf16_path": "hipblaslt",
                   "bf16_us": round(lib_us, 2), "w4_widen_us": round(wide_us, 2),
                   "widen_slowdown_vs_bf16": round(wide_us / lib_us, 3)})
+        mid = [int(m) for m in a.mid_ms.split(",") if m]
+        if mid:
+            silu = name == "gate_up"
+            k = torch.ops.kgc
+            gemm.pack_w4_decode_weights([] if silu else q4[:nb], q4[:nb] if silu else [])
+            gemm.pack_w8_decode_weights([] if silu else q8[:nb], q8[:nb] if silu else [])
+            p4 = [gemm.w4_packed_weight(w, silu) for w in q4[:nb]]
+            p8 = [gemm.w8_packed_weight(w, silu) for w in q8[:nb]]
+            s8 = [gemm._q_packed_entry(w, silu)[2] if silu else w.w8_scale for w in q8[:nb]]
+        for M in mid:
+            x = torch.randn(M, K, dtype=dt, device=dev)
+            No = N // 2 if silu else N
+            red = torch.empty(M, No, dtype=dt, device=dev)
+
+            def lib():
+                for w in ws[:nb]:
+                    y = F.linear(x, w)
+                    if silu:
+                        ops.silu_mul(y, red)
+
+            def wide():
+                for w in q4[:nb]:
+                    y = gemm.w4_widen_linear(x, w, w.w4_scale)
+                    if silu:
+                        ops.silu_mul(y, red)
+
+            def kern(launch, cfg, S):
+                buf = (torch.empty(S, M, N, dtype=torch.float32, device=dev) if S > 1 else
+                       torch.empty(M, No, dtype=dt, device=dev))
+
+                def run():
+                    for i in range(nb):
+                        launch(buf, i, cfg, 0 if S > 1 else (2 if silu else 1))
+                        if S > 1 and silu:
+                            k.splitk_reduce_silu(red, buf, True)
+                        elif S > 1:
+                            k.splitk_reduce(red, buf)
+                return gemm._time_graphed(run, 5) * 1e3 / nb
+            lib_us = gemm._time_graphed(lib, 5) * 1e3 / nb
+            wide_us = gemm._time_graphed(wide, 5) * 1e3 / nb
+            f_us = {(c, S): kern(lambda b, i, c, e: k.w4_dgemm(b, x, p4[i], None, c, e), c, S)
+                    for c, S in gemm._q_dg_candidates(M, N, K, gemm._w4_dg_tiles())}
+            q_us = {(c, S): kern(lambda b, i, c, e: k.w8_dgemm(
+                        b, x, p8[i], s8[i] if silu and e == 0 else q8[i].w8_scale, None, c, e), c, S)
+                    for c, S in gemm._q_dg_candidates(M, N, K, gemm._w8_dg_tiles())}
+            fb, qb = min(f_us, key=f_us.get), min(q_us, key=q_us.get)
+            emit({"gemm": name, "M": M, "N": N, "K": K, "consumer": "silu" if silu else "plain",
+                  "bf16_us": round(lib_us, 2), "w4_widen_us": round(wide_us, 2),
+                  "k9mf_us": {f"{c}/{S}": round(t, 2) for (c, S), t in sorted(f_us.items())},
+                  "k9mf_best": list(fb), "k9mf_best_us": round(f_us[fb], 2),
+                  "k9mq_best": list(qb), "k9mq_best_us": round(q_us[qb], 2),
+                  "k9mf_speedup_vs_widen": round(wide_us / f_us[fb], 3),
+                  "k9mf_speedup_vs_k9mq": round(q_us[qb] / f_us[fb], 3),
+                  "k9mf_speedup_vs_bf16": round(lib_us / f_us[fb], 3)})
         del ws, q8, q4
         torch.cuda.empty_cache()
 

@@ -10,8 +10,9 @@ once with ``--quantization fp8``, back to back on the same GPU.  Batches above 6
 512) run the mid-batch decode GEMMs: K9m for bf16 weights, K9mq or the widen path for fp8
 ones, and each line then carries the W8 plan of its bucket (``w8_plan``: shape and kind ->
 [cfg, S], or "widen").  With ``--quantization mxfp4`` a line of a batch <= 64 carries the W4
-plan of its bucket (``w4_plan``: shape -> K9f [mt, nt, nw], or "widen"); larger batches take
-the widen path.  ``--tag`` labels the lines, ``--out`` appends them to a file.
+plan of its bucket (``w4_plan``: shape -> K9f [mt, nt, nw], or "widen"); a larger batch the
+K9mf plan of its bucket (``w4_dg_plan``: shape and kind -> [cfg, S], or "widen").  ``--tag``
+labels the lines, ``--out`` appends them to a file.
 """
 import argparse
 import json
@@ -80,6 +81,10 @@ def main():
         if a.quantization == "fp8" and B > 64:
             rec["w8_plan"] = {f"{N}x{K}:{kind}": list(v) if v else "widen"
                               for (M, N, K, kind), v in sorted(w8_plan.items()) if M == B}
+        if a.quantization == "mxfp4" and B > 64:
+            rec["w4_dg_plan"] = {f"{N}x{K}:{kind}": list(v) if v else "widen"
+                                 for (M, N, K, kind), v in
+                                 sorted(getattr(gemm, "w4_dg_plan", dict)().items()) if M == B}
         if a.quantization == "mxfp4" and B <= 64:
             rec["w4_plan"] = {f"{N}x{K}": list(v) if v else "widen"
                               for (M, N, K), v in sorted(gemm.w4_plan().items()) if M == B}
