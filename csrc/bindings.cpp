@@ -418,6 +418,72 @@ void sample_vp_unpack(Tensor out, Tensor packed) {
                                (int)packed.numel(), stream());
 }
 
+// ---- K15 prompt logprobs
+int64_t plp_splits(int64_t R, int64_t ncols) { return kgc::plp_splits((int)R, (int)ncols); }
+
+// rec [R, S, 3 + 2k] fp32 <- logits [R, >= ncols] (any row stride / element offset)
+void plp_partial(Tensor rec, Tensor logits, Tensor targets, int64_t vocab_off, int64_t ncols,
+                 int64_t k) {
+  check_gpu(logits, "logits");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  check_same_dev(logits, rec, "rec");
+  check_same_dev(logits, targets, "targets");
+  TORCH_CHECK(logits.dim() == 2 && (logits.size(1) <= 1 || logits.stride(1) == 1),
+              "kgc.plp_partial: logits [R, V] with dense rows");
+  const int64_t R = logits.size(0);
+  TORCH_CHECK(k >= 0 && k <= 20, "kgc.plp_partial: k in 0..20");
+  TORCH_CHECK(ncols >= 0 && ncols <= logits.size(1), "kgc.plp_partial: ncols out of range");
+  TORCH_CHECK(vocab_off >= 0 && vocab_off + ncols < INT32_MAX, "kgc.plp_partial: vocab_off");
+  TORCH_CHECK(logits.stride(0) >= 0 && (R <= 1 || logits.stride(0) >= ncols),
+              "kgc.plp_partial: overlapping rows");
+  TORCH_CHECK(targets.scalar_type() == at::kLong && targets.is_contiguous() &&
+              targets.numel() == R, "kgc.plp_partial: targets int64 [R]");
+  TORCH_CHECK(rec.scalar_type() == at::kFloat && rec.is_contiguous() && rec.dim() == 3 &&
+              rec.size(0) == R && rec.size(2) == 3 + 2 * k, "kgc.plp_partial: rec [R, S, 3 + 2k]");
+  const int64_t S = rec.size(1);
+  TORCH_CHECK(S >= 1 && S <= 65535 && (ncols + S - 1) / S <= kgc::plp_cap(),
+              "kgc.plp_partial: a slice of ncols / S columns must fit ", kgc::plp_cap());
+  TORCH_CHECK(R < INT32_MAX, "kgc.plp_partial: rows");
+  if (R == 0) return;
+  kgc::launch_plp_partial(dt_code(logits), rec.data_ptr<float>(), logits.data_ptr(),
+                          logits.stride(0), targets.data_ptr<int64_t>(), (int)R, (int)S,
+                          (int)vocab_off, (int)ncols, (int)k, stream());
+}
+
+// rec [R, N, 3 + 2k] -> tok_lp [R], top_lp [R, k], top_id [R, k] (int32); or out_rec [R, 3 + 2k]
+void plp_merge(Tensor tok_lp, Tensor top_lp, Tensor top_id, std::optional<Tensor> out_rec,
+               Tensor rec, int64_t k) {
+  check_gpu(rec, "rec");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(rec.device());
+  TORCH_CHECK(k >= 0 && k <= 20, "kgc.plp_merge: k in 0..20");
+  TORCH_CHECK(rec.scalar_type() == at::kFloat && rec.is_contiguous() && rec.dim() == 3 &&
+              rec.size(2) == 3 + 2 * k && rec.size(1) >= 1, "kgc.plp_merge: rec [R, N, 3 + 2k]");
+  const int64_t R = rec.size(0), N = rec.size(1);
+  TORCH_CHECK(R < INT32_MAX && N * k < INT32_MAX, "kgc.plp_merge: shape");
+  float* orec = nullptr;
+  if (out_rec.has_value()) {
+    check_same_dev(rec, *out_rec, "out_rec");
+    TORCH_CHECK(out_rec->scalar_type() == at::kFloat && out_rec->is_contiguous() &&
+                out_rec->numel() == R * (3 + 2 * k), "kgc.plp_merge: out_rec [R, 3 + 2k]");
+    orec = out_rec->data_ptr<float>();
+  } else {
+    check_same_dev(rec, tok_lp, "tok_lp");
+    check_same_dev(rec, top_lp, "top_lp");
+    check_same_dev(rec, top_id, "top_id");
+    TORCH_CHECK(tok_lp.scalar_type() == at::kFloat && tok_lp.is_contiguous() && tok_lp.numel() == R,
+                "kgc.plp_merge: tok_lp fp32 [R]");
+    TORCH_CHECK(top_lp.scalar_type() == at::kFloat && top_lp.is_contiguous() &&
+                top_lp.numel() == R * k, "kgc.plp_merge: top_lp fp32 [R, k]");
+    TORCH_CHECK(top_id.scalar_type() == at::kInt && top_id.is_contiguous() &&
+                top_id.numel() == R * k, "kgc.plp_merge: top_id int32 [R, k]");
+  }
+  if (R == 0) return;
+  kgc::launch_plp_merge(orec ? nullptr : tok_lp.data_ptr<float>(),
+                        orec ? nullptr : top_lp.data_ptr<float>(),
+                        orec ? nullptr : top_id.data_ptr<int>(), orec, rec.data_ptr<float>(),
+                        (int)R, (int)N, (int)k, stream());
+}
+
 // ---- K13/K14 MoE
 void moe_route(Tensor topk_w, Tensor topk_ids, Tensor logits, bool renorm) {
   check_gpu(logits, "logits");
@@ -1562,6 +1628,11 @@ TORCH_LIBRARY(kgc, m) {
   m.def("sample_vp(Tensor(a!) packed, Tensor logits, int V, Tensor temperature, Tensor seeds, "
         "int vocab_off) -> ()");
   m.def("sample_vp_unpack(Tensor(a!) out, Tensor packed) -> ()");
+  m.def("plp_splits(int R, int ncols) -> int", &plp_splits);
+  m.def("plp_partial(Tensor(a!) rec, Tensor logits, Tensor targets, int vocab_off, int ncols, "
+        "int k) -> ()");
+  m.def("plp_merge(Tensor(a!) tok_lp, Tensor(b!) top_lp, Tensor(c!) top_id, Tensor(d!)? out_rec, "
+        "Tensor rec, int k) -> ()");
   m.def("decode_wave_min_pairs() -> int", &decode_wave_min_pairs);
   m.def("moe_route(Tensor(a!) topk_w, Tensor(b!) topk_ids, Tensor logits, bool renorm) -> ()");
   m.def("moe_gate_route(Tensor(a!) topk_w, Tensor(b!) topk_ids, Tensor x, Tensor wg, "
@@ -1667,6 +1738,8 @@ TORCH_LIBRARY_IMPL(kgc, CUDA, m) {
   m.impl("sample", &sample);
   m.impl("sample_vp", &sample_vp);
   m.impl("sample_vp_unpack", &sample_vp_unpack);
+  m.impl("plp_partial", &plp_partial);
+  m.impl("plp_merge", &plp_merge);
   m.impl("xgmi_allreduce", &xgmi_allreduce);
   m.impl("xgmi_allreduce_rms", &xgmi_allreduce_rms);
   m.impl("xgmi_allreduce_emu", &xgmi_allreduce_emu);

@@ -93,6 +93,19 @@ void launch_sample_vp(int dtype, int64_t* packed, uint64_t* partial, const void*
                       const int64_t* seeds, int vocab_off, hipStream_t s);
 void launch_sample_vp_unpack(int64_t* out, const int64_t* packed, int B, hipStream_t s);
 
+// K15 prompt logprobs.  Stage 1: rec [R, S, 3 + 2k] fp32 words (m, s, t, k values, k global
+// column ids as int bits) over columns [0, ncols) of logits [R, >= ncols]; every slice
+// ncols / S must fit plp_cap() columns (plp_splits gives a valid S).  Stage 2: the N
+// records of each row -> tok_lp [R], top_lp / top_id [R, k], or (out_rec != null) one
+// merged record [R, 3 + 2k].
+int plp_splits(int R, int ncols);
+int plp_cap();
+void launch_plp_partial(int dtype, float* rec, const void* logits, int64_t row_stride,
+                        const int64_t* targets, int R, int S, int vocab_off, int ncols, int k,
+                        hipStream_t s);
+void launch_plp_merge(float* tok_lp, float* top_lp, int* top_id, float* out_rec, const float* rec,
+                      int R, int N, int k, hipStream_t s);
+
 // K9 skinny (small-M decode) GEMM: C[M, N] = X[M, K] . W[N, K]^T (+ bias), M <= 16*mt.
 // epi: 0 plain, 1 RMS-normalise X rows on the fly (gamma [K], eps), 2 accumulate into C,
 // 3 silu(gate) * up over a merged weight (C [M, N/2]), 4 accumulate into C then

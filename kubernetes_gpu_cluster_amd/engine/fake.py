@@ -53,6 +53,7 @@ class FakeOutput:
     num_preemptions: int = 0
     logprobs: Optional[list] = None
     num_output_tokens: int = 0
+    prompt_logprobs: Optional[list] = None     # accepted in the request, never computed
 
 
 def timing_from_env(spec: str) -> tuple[float, float, float]:

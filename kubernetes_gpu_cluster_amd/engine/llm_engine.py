@@ -131,6 +131,8 @@ class LLMEngine:
         if self.pp_depth > 1 and params.logprobs is not None:
             # the pipelined path returns only the sampled ids from the last stage
             raise ValueError("logprobs are not supported with pipeline_parallel_size > 1")
+        if self.pp_depth > 1 and params.prompt_logprobs is not None:
+            raise ValueError("prompt_logprobs are not supported with pipeline_parallel_size > 1")
         seq = Sequence(rid, prompt_token_ids, params, arrival_time, self.max_model_len)
         self.seqs[rid] = seq
         self.scheduler.add(seq)
@@ -286,6 +288,8 @@ class LLMEngine:
         fut, samplers, plan, t0, npre = inflight
         tokens = fut.result()
         lps = fut.logprobs() if plan.lp else {}
+        if plan.plp:
+            self._collect_prompt_logprobs(plan, fut.prompt_logprobs())
         now = time.monotonic()
         outs: list[RequestOutput] = []
         for row, (seq, tok) in enumerate(zip(samplers, tokens)):
@@ -320,6 +324,8 @@ class LLMEngine:
                               seq.num_preemptions)
             if row in lps:
                 o.logprobs = [(tok, lps[row][0], lps[row][1])]
+            if idx == 0:
+                o.prompt_logprobs = seq.plp
             outs.append(o)
         self.metrics.on_step(plan, now - t0, len(samplers), self.bm.usage(),
                              len(self.scheduler.running), len(self.scheduler.waiting), npre)
@@ -335,6 +341,9 @@ class LLMEngine:
         plan, samplers = self.executor.runner.build_plan(batch.prefills, batch.decodes, self.bm.table)
         tokens = self.executor.execute(plan)
         lps = TokenFuture(None, lp=self.executor.runner.take_logprobs()).logprobs() if plan.lp else {}
+        if plan.plp:
+            self._collect_prompt_logprobs(plan, TokenFuture(
+                None, plp=self.executor.runner.take_prompt_logprobs()).prompt_logprobs())
         now = time.monotonic()
         for seq, n in batch.prefills:
             seq.num_computed += n
@@ -364,11 +373,25 @@ class LLMEngine:
                               seq.num_preemptions)
             if row in lps:
                 o.logprobs = [(tok, lps[row][0], lps[row][1])]
+            if len(seq.output_token_ids) == 1:
+                o.prompt_logprobs = seq.plp
             outs.append(o)
         self.metrics.on_step(plan, now - t0, len(samplers), self.bm.usage(),
                              len(self.scheduler.running), len(self.scheduler.waiting),
                              len(batch.preempted))
         return outs
+
+    @staticmethod
+    def _collect_prompt_logprobs(plan, data) -> None:
+        """File a step's prompt-logprob rows (plan.plp order) under their sequences: row j
+        of a chunk that reports from position s is the entry of prompt token s + j + 1."""
+        tok, top, ids = data
+        r = 0
+        for seq, s, cnt, k in plan.plp:
+            for p in range(s + 1, s + cnt + 1):
+                alts = [(i, v) for i, v in zip(ids[r][:k], top[r][:k]) if i >= 0]
+                seq.plp[p] = (seq.prompt_token_ids[p], tok[r], alts)
+                r += 1
 
     def _check_stop(self, seq: Sequence, tok: int) -> Optional[str]:
         p = seq.params
@@ -414,14 +437,18 @@ class LLM:
             ids.append(str(i))
         final: dict[str, RequestOutput] = {}
         lps: dict[str, list] = {}
+        plps: dict[str, list] = {}
         while self.engine.has_unfinished():
             for o in self.engine.step():
                 if o.logprobs:
                     lps.setdefault(o.request_id, []).extend(o.logprobs)
+                if o.prompt_logprobs is not None:
+                    plps[o.request_id] = o.prompt_logprobs
                 if o.finished:
                     final[o.request_id] = o
         for rid, o in final.items():
             o.logprobs = lps.get(rid)
+            o.prompt_logprobs = plps.get(rid)
         return [final[i] for i in ids]
 
     def shutdown(self):

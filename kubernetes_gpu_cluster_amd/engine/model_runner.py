@@ -60,6 +60,7 @@ class StepPlan:
     lp: Optional[list] = None   # driver only: [(sampled row, top-k)] for logprobs requests
     proc: Optional[list] = None  # driver only: [(sampled row, slot, params)] penalties/bias/min_p
     proc_init: Optional[list] = None  # driver only: [(slot, prompt ids, output ids)]
+    plp: Optional[list] = None  # driver only: [(seq, first prompt position, rows, k)] prompt logprobs
 
     def header(self) -> list[int]:
         return [self.T, self.Tp, self.P, self.D, self.S, self.W, self.B, self.max_ctx,
@@ -90,6 +91,10 @@ class Layout:
         self.ws, o = o, o + self.Wmax
         self.wm, o = o, o + self.Wmax
         self.topk, o = o, o + self.Smax
+        # prompt logprobs, four rows of Smax, one entry per prefill sequence: 0 / k + 1
+        # (wanted, with k alternatives); the first row of its chunk that reports; how many
+        # rows report; the target of the last one when the chunk ends before it (else -1)
+        self.plp, o = o, o + 4 * self.Smax
         self.n32 = o
         self.temp, self.topp = 0, self.Smax
         self.nf = 2 * self.Smax
@@ -150,7 +155,8 @@ class ModelRunner:
                          for _ in range(2)]
         self._tok_flip = 0
         self.stats = {"graph_steps": 0, "eager_steps": 0, "vp_steps": 0,
-                      "tp_allreduce_bytes": 0, "tp_logits_bytes": 0}
+                      "tp_allreduce_bytes": 0, "tp_logits_bytes": 0,
+                      "plp_rows": 0, "tp_plp_bytes": 0}
         # KGC_FAKE_STAGE_MS: every step of this rank is a sleep of that many ms with the
         # real pipeline-stage traffic around it (PP scheduling / utilisation tests)
         self._fake_ms = float(os.environ.get("KGC_FAKE_STAGE_MS", "0") or 0)
@@ -166,6 +172,18 @@ class ModelRunner:
             self.vp_off = head.start
             self.vp_cols = max(0, min(head.per, head.vocab - head.start))
             self.vp_packed = torch.zeros(max_num_seqs, dtype=torch.int64, device=device)
+        # prompt logprobs (K15): every TP rank works on its own vocabulary shard and the
+        # ranks exchange one record per row; the LM head runs on at most plp_rows prompt
+        # positions at a time (KGC_PLP_LOGITS_MB of logits, from the caching allocator)
+        self.plp_shard = self.ps.tp_size > 1 and head is not None and hasattr(head, "start")
+        self.plp_off = head.start if self.plp_shard else 0
+        self.plp_cols = (max(0, min(head.per, head.vocab - head.start)) if self.plp_shard
+                         else mcfg.vocab_size)
+        vloc = head.per if self.plp_shard else mcfg.vocab_size
+        cap = int(float(os.environ.get("KGC_PLP_LOGITS_MB", "128")) * (1 << 20))
+        rows = max(1, cap // (vloc * torch.finfo(dtype).bits // 8))
+        self.plp_rows = rows // 64 * 64 if rows >= 64 else rows
+        self._last_plp = None
 
     def _blob_offsets(self):
         up = lambda n: (n + 255) // 256 * 256    # noqa: E731
@@ -278,6 +296,7 @@ class ModelRunner:
         i64[L.lidx:L.lidx + P] = qsl[1:] - 1
         self.hf.numpy()[: 2 * self.L.Smax] = 1.0
         i64[L.sslots:L.sslots + P] = 0
+        i32[L.plp:L.plp + 4 * L.Smax] = 0          # no prompt logprobs
         # (no TP overlap split in the profiling step: every rank runs it from its own
         # copy, and the unsplit step's activations are the larger ones)
         plan = StepPlan(T, T, P, 0, P, len(ws), 0, 0, 0, 0, int(self.vp), 0, i64, i32,
@@ -315,6 +334,7 @@ class ModelRunner:
                 lidx.append(off - 1)
         Tp = off
         W = 0
+        plp = self._plan_prompt_logprobs(prefills, i32) if P else None
         if P:
             i32[L.qsl:L.qsl + P + 1] = np.concatenate([[0], np.cumsum(qlens)])
             i32[L.sl:L.sl + P] = slens
@@ -389,7 +409,34 @@ class ModelRunner:
         # all-reduces of different sizes (a hang or a corrupt step)
         split = int(P > 0 and D == 0 and self._overlap_ok(Tp))
         return StepPlan(T, Tp, P, D, S, W, B, max_ctx, int(device_tokens and D > 0), bcast, vp,
-                        split, i64, i32, f32, lp, proc, proc_init), samplers
+                        split, i64, i32, f32, lp, proc, proc_init, plp), samplers
+
+    def _plan_prompt_logprobs(self, prefills, i32: np.ndarray) -> Optional[list]:
+        """Write the step's prompt-logprobs section (every step with prefills: the ring's
+        blobs hold older steps) and advance each sequence's count of reported positions.
+        Position i of a prompt of n tokens predicts token i + 1: a chunk over [a, b)
+        reports rows max(a, reported) .. min(b, n - 1) - 1; the row that predicts the first
+        generated token is the sampled row."""
+        L, P = self.L, len(prefills)
+        sec = i32[L.plp:L.plp + 4 * L.Smax].reshape(4, L.Smax)
+        sec[:, :P] = 0
+        sec[3, :P] = -1
+        plp = []
+        for i, (seq, n) in enumerate(prefills):
+            k = seq.params.prompt_logprobs
+            if k is None:
+                continue
+            a, b = seq.num_computed, seq.num_computed + n
+            s, e = max(a, seq.plp_next), min(b, seq.num_prompt - 1)
+            sec[0, i] = k + 1
+            if e <= s:
+                continue
+            sec[1, i], sec[2, i] = s - a, e - s
+            if e == b:                       # the target is the first token of the next chunk
+                sec[3, i] = seq.prompt_token_ids[e]
+            plp.append((seq, s, e - s, k))
+            seq.plp_next = e
+        return plp or None
 
     # ------------------------------------------------------------------ execution (all ranks)
     def _upload(self, plan: StepPlan) -> None:
@@ -524,6 +571,7 @@ class ModelRunner:
         if self._fake_ms:
             return self._run_fake(plan)
         self._upload(plan)
+        self._last_plp = None
         L = self.L
         ps = self.ps
         hidden_in = None
@@ -558,6 +606,8 @@ class ModelRunner:
             if not self.model.last:
                 comm.pp_send(list(out))
                 return None
+            if plan.P:
+                self._prompt_logprobs(plan, out)
             idx = self.d64[L.lidx:L.lidx + plan.S]
             logits = self.model.compute_logits(out.index_select(0, idx), gather=not self.vp)
         if ps.tp_size > 1:
@@ -674,6 +724,72 @@ class ModelRunner:
         lp, rows, lsm, topv, topi = pre
         chosen = lsm.gather(1, res.index_select(0, rows).view(-1, 1)).view(-1)
         return lp, chosen, topv, topi
+
+    # ------------------------------------------------------------------ prompt logprobs
+    def _prompt_logprobs(self, plan: StepPlan, hidden: torch.Tensor) -> None:
+        """Log-probabilities of the prompt tokens this step's prefill chunks predict
+        (K15), for the sequences the plan's section marks.  The row list comes from this
+        rank's own copy of the blobs.  The LM head runs on at most ``plp_rows`` positions
+        at a time; at TP > 1 the ranks all-gather one (3 + 2k)-word record per row, never
+        logits.  Results go to pinned host buffers by non-blocking copies, behind which
+        the step's token event is recorded (tokens_to_host)."""
+        L, P = self.L, plan.P
+        sec = plan.i32[L.plp:L.plp + 4 * L.Smax].reshape(4, L.Smax)[:, :P]
+        want = np.flatnonzero((sec[0] > 0) & (sec[2] > 0))
+        if want.size == 0:
+            return
+        k = int(sec[0].max()) - 1
+        qsl = plan.i32[L.qsl:L.qsl + P]
+        ids = plan.i64[L.ids:L.ids + plan.Tp]
+        rows, tgt = [], []
+        for i in want:
+            r0, n = int(qsl[i]) + int(sec[1, i]), int(sec[2, i])
+            rows.append(np.arange(r0, r0 + n, dtype=np.int64))
+            if sec[3, i] >= 0:
+                tgt.append(ids[r0 + 1:r0 + n])
+                tgt.append(np.asarray([sec[3, i]], dtype=np.int64))
+            else:
+                tgt.append(ids[r0 + 1:r0 + n + 1])
+        flat = np.concatenate(rows + tgt)
+        R = flat.size // 2
+        if self.is_gpu:
+            # a fresh pinned block per step: the host allocator keeps it until the copy ran
+            host = torch.empty(2 * R, dtype=torch.int64, pin_memory=True)
+            host.numpy()[:] = flat
+            dev = host.to(self.device, non_blocking=True)
+        else:
+            dev = torch.from_numpy(flat)
+        tp, W = self.ps.tp_size, 3 + 2 * k
+        outs = []
+        for c0 in range(0, R, self.plp_rows):
+            c1 = min(R, c0 + self.plp_rows)
+            h = hidden.index_select(0, dev[c0:c1])
+            logits = self.model.compute_logits(h, gather=not self.plp_shard)
+            rec = ops.prompt_logprobs_partial(logits, dev[R + c0:R + c1], self.plp_off,
+                                              self.plp_cols, k)
+            del logits
+            if self.plp_shard:
+                one = ops.prompt_logprobs_merge(rec, k, as_record=True)
+                rec = comm.tp_all_gather(one, 1).view(c1 - c0, tp, W)
+                self.stats["tp_plp_bytes"] += (c1 - c0) * W * 4
+            outs.append(ops.prompt_logprobs_merge(rec, k))
+        self.stats["plp_rows"] += R
+        tok, top, tid = (torch.cat(x) if len(outs) > 1 else x[0] for x in zip(*outs))
+        res = []
+        for t in (tok, top, tid):
+            if self.is_gpu:
+                hb = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+                hb.copy_(t, non_blocking=True)
+                res.append(hb)
+            else:
+                res.append(t)
+        self._last_plp = tuple(res)
+
+    def take_prompt_logprobs(self):
+        """(token logprob [R], top logprobs [R, k], top ids [R, k]) host tensors of the last
+        step, rows in the plan's order; valid once the step's tokens have been read."""
+        r, self._last_plp = self._last_plp, None
+        return r
 
     def take_logprobs(self):
         lp, self._last_lp = getattr(self, "_last_lp", None), None

@@ -150,7 +150,10 @@ class Scheduler:
             while self.waiting and budget > 0 and len(self.running) < self.max_num_seqs:
                 seq = self.waiting[0]
                 # prefix caching: leading full blocks already in the cache are not recomputed
-                hits = self.bm.cached_prefix_blocks(seq) if self.bm.prefix_caching else []
+                # (a sequence that reports prompt logprobs computes every position: no hits;
+                # it still publishes its blocks)
+                hits = (self.bm.cached_prefix_blocks(seq)
+                        if self.bm.prefix_caching and seq.params.prompt_logprobs is None else [])
                 start = seq.num_computed + len(hits) * bs
                 remaining = seq.num_tokens - start
                 n = min(remaining, budget)

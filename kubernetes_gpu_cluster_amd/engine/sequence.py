@@ -8,6 +8,7 @@ import time
 from typing import Optional
 
 _seq_ids = itertools.count()
+MAX_LOGPROBS = 20          # alternatives per token (logprobs, prompt_logprobs): K15's k range
 
 
 @dataclasses.dataclass
@@ -28,6 +29,9 @@ class SamplingParams:
     repetition_penalty: float = 1.0
     min_p: float = 0.0
     logit_bias: Optional[dict] = None
+    # log-probability of every prompt token but the first, each with this many
+    # alternatives (vLLM's prompt_logprobs; None: off)
+    prompt_logprobs: Optional[int] = None
     needs_proc: bool = dataclasses.field(default=False, init=False, repr=False)
 
     def __post_init__(self):
@@ -47,6 +51,8 @@ class SamplingParams:
             raise ValueError("repetition_penalty must be > 0")
         if not 0.0 <= self.min_p <= 1.0:
             raise ValueError("min_p must be in [0, 1]")
+        if self.prompt_logprobs is not None and not 0 <= self.prompt_logprobs <= MAX_LOGPROBS:
+            raise ValueError(f"prompt_logprobs must be in [0, {MAX_LOGPROBS}]")
         if self.logit_bias:
             for k, v in self.logit_bias.items():
                 if not -100 <= float(v) <= 100:
@@ -69,7 +75,8 @@ class Sequence:
                  "status", "block_ids", "num_computed", "arrival_time", "first_token_time",
                  "finish_time", "finish_reason", "seed", "num_preemptions", "max_tokens",
                  "slot", "last_token_time", "token_times", "prompt_text", "stream",
-                 "num_pending", "proc_slot", "block_keys", "num_registered", "vengine")
+                 "num_pending", "proc_slot", "block_keys", "num_registered", "vengine",
+                 "plp_next", "plp")
 
     def __init__(self, request_id: str, prompt_token_ids: list[int], params: SamplingParams,
                  arrival_time: Optional[float] = None, max_model_len: int = 1 << 30):
@@ -99,6 +106,11 @@ class Sequence:
         self.block_keys: list[bytes] = []       # prefix-cache keys of its full blocks
         self.num_registered = 0               # leading blocks published to the prefix cache
         self.vengine = 0                      # PP micro-batch (engine/scheduler.VirtualSchedulers)
+        # prompt logprobs: positions [0, plp_next) have been requested from the runner (kept
+        # over a recompute preemption), and the entries collected so far, one per prompt token
+        self.plp_next = 0
+        self.plp: Optional[list] = ([None] * len(self.prompt_token_ids)
+                                    if params.prompt_logprobs is not None else None)
 
     @property
     def num_tokens(self) -> int:
@@ -149,6 +161,10 @@ class RequestOutput:
     # per new token, when the request asked for logprobs:
     # (token id, logprob, [(alternative id, logprob)] top-k)
     logprobs: Optional[list] = None
+    # on the output that carries the request's first token, when it asked for
+    # prompt_logprobs: one entry per prompt token, None for the first, then
+    # (token id, logprob, [(alternative id, logprob)] top-k)
+    prompt_logprobs: Optional[list] = None
 
     @property
     def output_token_ids(self) -> list[int]:

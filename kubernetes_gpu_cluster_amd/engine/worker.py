@@ -374,7 +374,7 @@ class LocalExecutor:
         slot = sh.enqueue_err_read() if sh is not None else None
         done = (lambda: sh.raise_if_failed(slot)) if sh is not None else None
         return TokenFuture(*self.runner.tokens_to_host(out), lp=self.runner.take_logprobs(),
-                           on_done=done)
+                           on_done=done, plp=self.runner.take_prompt_logprobs())
 
     @property
     def supports_async(self) -> bool:
@@ -392,8 +392,9 @@ class TokenFuture:
     completed on the device (failure checks: engine/health.py)."""
 
     def __init__(self, buf: torch.Tensor, ev=None, values: Optional[list[int]] = None, lp=None,
-                 on_done=None):
+                 on_done=None, plp=None):
         self.buf, self.ev, self.values, self._lp = buf, ev, values, lp
+        self._plp = plp        # ModelRunner.take_prompt_logprobs(): pinned host tensors
         self._on_done = on_done
 
     def done(self) -> bool:
@@ -417,6 +418,15 @@ class TokenFuture:
         chosen, topv, topi = chosen.tolist(), topv.tolist(), topi.tolist()
         return {r: (chosen[i], list(zip(topi[i][:k], topv[i][:k])))
                 for i, (r, k) in enumerate(rows)}
+
+    def prompt_logprobs(self):
+        """(token logprobs [R], top logprobs [R][k], top ids [R][k]) as lists, rows in the
+        order of the plan's ``plp``; read after ``result()`` (the copies land before the
+        token copy's event)."""
+        if self._plp is None:
+            return [], [], []
+        tok, top, ids = self._plp
+        return tok.tolist(), top.tolist(), ids.tolist()
 
 
 class PipelinedTokenFuture:
@@ -527,7 +537,7 @@ class _DistExecutorBase:
         if self.watchdog is not None:
             self.watchdog.step_end()
         return TokenFuture(*self.runner.tokens_to_host(out), lp=self.runner.take_logprobs(),
-                           on_done=self._step_launched())
+                           on_done=self._step_launched(), plp=self.runner.take_prompt_logprobs())
 
     def execute(self, plan: StepPlan) -> list[int]:
         if self.watchdog is not None:

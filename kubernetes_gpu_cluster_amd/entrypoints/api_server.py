@@ -73,6 +73,7 @@ class CompletionRequest(_Lenient):
     min_tokens: int = 0
     echo: bool = False
     logprobs: Optional[int] = None
+    prompt_logprobs: Optional[int] = None
     presence_penalty: Optional[float] = 0.0
     frequency_penalty: Optional[float] = 0.0
     repetition_penalty: Optional[float] = 1.0
@@ -104,6 +105,7 @@ class ChatCompletionRequest(_Lenient):
     min_tokens: int = 0
     logprobs: bool = False
     top_logprobs: Optional[int] = None
+    prompt_logprobs: Optional[int] = None
     presence_penalty: Optional[float] = 0.0
     frequency_penalty: Optional[float] = 0.0
     repetition_penalty: Optional[float] = 1.0
@@ -196,19 +198,32 @@ def build_app(engine: AsyncLLMEngine, tokenizer, served_name: str, max_model_len
         stops = req.stop if isinstance(req.stop, list) else ([req.stop] if req.stop else [])
         if logprobs is not None and not 0 <= logprobs <= MAX_LOGPROBS:
             raise ValueError(f"logprobs must be in [0, {MAX_LOGPROBS}]")
+        plp = req.prompt_logprobs
+        if plp is not None and not 0 <= plp <= MAX_LOGPROBS:
+            raise ValueError(f"prompt_logprobs must be in [0, {MAX_LOGPROBS}]")
+        if logprobs is not None and getattr(req, "echo", False) and not req.stream:
+            # echo + logprobs: the logprobs arrays cover the echoed prompt too (streams do
+            # not echo)
+            plp = max(plp or 0, logprobs)
         return SamplingParams(temperature=req.temperature if req.temperature is not None else 1.0,
                               top_p=req.top_p if req.top_p is not None else 1.0,
                               top_k=req.top_k if req.top_k not in (None, 0) else -1,
                               max_tokens=max_tokens, min_tokens=req.min_tokens,
                               stop_token_ids=list(req.stop_token_ids or []), stop=stops,
                               ignore_eos=req.ignore_eos, seed=req.seed, n=req.n,
-                              logprobs=logprobs,
+                              logprobs=logprobs, prompt_logprobs=plp,
                               presence_penalty=req.presence_penalty or 0.0,
                               frequency_penalty=req.frequency_penalty or 0.0,
                               repetition_penalty=req.repetition_penalty or 1.0,
                               min_p=req.min_p or 0.0,
                               logit_bias={int(k): float(v) for k, v in (req.logit_bias or {}).items()}
                               or None)
+
+    def choice_params(sp: SamplingParams, i: int) -> SamplingParams:
+        """Choice i of a prompt: its own seed; only choice 0 asks the engine for the
+        prompt's logprobs (the other choices of the prompt reuse its result)."""
+        return dataclasses.replace(sp, n=1, seed=None if sp.seed is None else sp.seed + i,
+                                   prompt_logprobs=sp.prompt_logprobs if i == 0 else None)
 
     def close_all(gens) -> None:
         """Abort every submitted choice that has not finished (no-op for finished ones)."""
@@ -231,8 +246,8 @@ def build_app(engine: AsyncLLMEngine, tokenizer, served_name: str, max_model_len
         """One engine request per choice (n > 1 fans out with seeds seed+i); choices stream
         interleaved, each chunk tagged with its choice index."""
         n = sp.n
-        subs = [dataclasses.replace(sp, n=1, seed=None if sp.seed is None else sp.seed + i)
-                for i in range(n)]
+        subs = [choice_params(sp, i) for i in range(n)]
+        want_plp = sp.prompt_logprobs is not None
         rids = [rid if n == 1 else f"{rid}-{i}" for i in range(n)]
         # submit every choice before the response starts (EngineDeadError -> 503 here)
         gens = [engine.generate(ids, subs[i], rids[i]) for i in range(n)]
@@ -252,7 +267,9 @@ def build_app(engine: AsyncLLMEngine, tokenizer, served_name: str, max_model_len
                             reason = "stop"
                         elif reason:
                             delta += detok.flush()
-                        if delta or reason or out.logprobs:
+                        if out.prompt_logprobs is not None:
+                            yield stream_fn(delta, reason, out.logprobs, 0, out.prompt_logprobs)
+                        elif delta or reason or out.logprobs:
                             yield stream_fn(delta, reason, out.logprobs, 0)
                         if detok.stopped:
                             break
@@ -282,6 +299,8 @@ def build_app(engine: AsyncLLMEngine, tokenizer, served_name: str, max_model_len
                             reason = "stop"
                         elif reason:
                             delta += detok.flush()
+                        if out.prompt_logprobs is not None:
+                            await q.put((i, None, "__plp__", out.prompt_logprobs))
                         if delta or reason or out.logprobs:
                             await q.put((i, delta, reason, out.logprobs))
                         if detok.stopped:
@@ -295,16 +314,36 @@ def build_app(engine: AsyncLLMEngine, tokenizer, served_name: str, max_model_len
             async def sse():
                 tasks = [asyncio.create_task(pump(i)) for i in range(n)]
                 done = 0
+                # prompt logprobs ride on each choice's first chunk; choice 0 computes them,
+                # so chunks that arrive before its result wait for it
+                plp, started, held, waiting = None, [False] * n, [], want_plp
                 try:
                     while done < n:
                         i, delta, reason, lps = await q.get()
                         if reason == "__done__":
                             done += 1
+                            if i == 0 and waiting:             # choice 0 ended without them
+                                waiting = False
+                                for h in held:
+                                    yield stream_fn(*h[1:], h[0])
+                                held = []
                             continue
                         if isinstance(lps, BaseException):
                             yield f"data: {json.dumps({'error': str(lps)})}\n\n"
                             continue
-                        yield stream_fn(delta, reason, lps, i)
+                        if reason == "__plp__":
+                            plp, waiting = lps, False
+                            for h in held:
+                                yield stream_fn(h[1], h[2], h[3], h[0],
+                                                None if started[h[0]] else plp)
+                                started[h[0]] = True
+                            held = []
+                            continue
+                        if waiting:
+                            held.append((i, delta, reason, lps))
+                            continue
+                        yield stream_fn(delta, reason, lps, i, None if started[i] else plp)
+                        started[i] = True
                     if include_usage:
                         yield usage_chunk(final_fn, len(ids), sum(ncs))
                     yield "data: [DONE]\n\n"
@@ -317,39 +356,65 @@ def build_app(engine: AsyncLLMEngine, tokenizer, served_name: str, max_model_len
         async def one(i):
             detok = _Detok(tokenizer, subs[i].stop)
             gen = gens[i]
-            last, lps = None, []
+            last, lps, plp = None, [], None
             async for out in gen:
                 last = out
                 if out.logprobs:
                     lps.extend(out.logprobs)
+                if out.prompt_logprobs is not None:
+                    plp = out.prompt_logprobs
                 detok.update(out.output_token_ids)
                 if detok.stopped:
                     await gen.aclose()
                     break
             reason = "stop" if detok.stopped else (last.finish_reason if last else None)
-            return detok.text, reason, (len(last.output_token_ids) if last else 0), lps
+            return detok.text, reason, (len(last.output_token_ids) if last else 0), lps, plp
         try:
             res = await asyncio.gather(*[one(i) for i in range(n)])
         finally:
             close_all(gens)      # a failed or cancelled sibling leaves the others unread
-        text, reason, nc, lps = res[0]
+        text, reason, nc, lps, plp = res[0]
         body = final_fn(text, reason, len(ids), sum(r[2] for r in res),
-                        lps if sp.logprobs is not None else None)
+                        lps if sp.logprobs is not None else None, plp)
         if n > 1:
             choices = []
-            for i, (t_i, r_i, _, l_i) in enumerate(res):
-                one_body = final_fn(t_i, r_i, len(ids), 0, l_i if sp.logprobs is not None else None)
+            for i, (t_i, r_i, _, l_i, _) in enumerate(res):
+                one_body = final_fn(t_i, r_i, len(ids), 0,
+                                    l_i if sp.logprobs is not None else None, plp)
                 c = one_body["choices"][0]
                 c["index"] = i
                 choices.append(c)
             body["choices"] = choices
         return JSONResponse(body)
 
-    def completion_logprobs(lps, offset0: int = 0):
-        """legacy completions shape: tokens / token_logprobs / top_logprobs / text_offset"""
+    def prompt_logprobs_json(plp, n: Optional[int]):
+        """vLLM's shape without rank: null, then per prompt token {"<id>": {"logprob",
+        "decoded_token"}} for the token itself and its n best alternatives."""
+        if plp is None or n is None:
+            return None
+
+        def ent(t, lp):
+            return {"logprob": lp, "decoded_token": tok_str(t)}
+        return [None if e is None else
+                {str(t): ent(t, lp) for t, lp in [(e[0], e[1])] + list(e[2][:n])} for e in plp]
+
+    def completion_logprobs(lps, offset0: int = 0, echo=None, n: int = 0):
+        """legacy completions shape: tokens / token_logprobs / top_logprobs / text_offset.
+        echo: (prompt ids, the prompt's logprobs) with echo=true: the arrays then cover the
+        echoed prompt, from offset 0 and with null for its first token, followed by the
+        generated tokens."""
         if lps is None:
             return None
         toks, vals, tops, offs = [], [], [], []
+        if echo is not None and echo[1] is not None:
+            off = 0
+            for t, e in zip(*echo):
+                s = tok_str(t)
+                toks.append(s)
+                vals.append(None if e is None else e[1])
+                tops.append(None if e is None else {tok_str(a): v for a, v in e[2][:n]})
+                offs.append(min(off, offset0))
+                off += len(s)
         off = offset0
         for t, lp, top in lps:
             s = tok_str(t)
@@ -388,16 +453,20 @@ def build_app(engine: AsyncLLMEngine, tokenizer, served_name: str, max_model_len
         subs, gens = [], []
         for pi, ids in enumerate(all_ids):
             for i in range(n):
-                sub = dataclasses.replace(sp, n=1, seed=None if sp.seed is None else sp.seed + i)
+                sub = choice_params(sp, i)
                 subs.append(sub)
                 gens.append(engine.generate(ids, sub, f"{rid}-{pi}-{i}"))
 
         async def drain(k, q=None):
             detok = _Detok(tokenizer, subs[k].stop)
-            gen, last, lps = gens[k], None, []
+            gen, last, lps, plp = gens[k], None, [], None
             try:
                 async for out in gen:
                     last = out
+                    if out.prompt_logprobs is not None:
+                        plp = out.prompt_logprobs
+                        if q is not None:
+                            await q.put((k, None, "__plp__", plp))
                     delta = detok.update(out.output_token_ids)
                     reason = out.finish_reason if out.finished else None
                     if detok.stopped:
@@ -419,7 +488,7 @@ def build_app(engine: AsyncLLMEngine, tokenizer, served_name: str, max_model_len
                 if q is not None:
                     await q.put((k, None, "__done__", None))
             reason = "stop" if detok.stopped else (last.finish_reason if last else None)
-            return detok.text, reason, (len(last.output_token_ids) if last else 0), lps
+            return detok.text, reason, (len(last.output_token_ids) if last else 0), lps, plp
 
         if req.stream:
             q: asyncio.Queue = asyncio.Queue()
@@ -429,6 +498,10 @@ def build_app(engine: AsyncLLMEngine, tokenizer, served_name: str, max_model_len
             async def sse():
                 tasks = [asyncio.create_task(drain(k, q)) for k in range(len(gens))]
                 done = 0
+                # a prompt's logprobs (computed by its choice 0) ride on the first chunk of
+                # each of its choices that starts after they arrived
+                plps: dict = {}
+                started = [False] * len(gens)
                 try:
                     while done < len(gens):
                         k, delta, reason, lps = await q.get()
@@ -438,10 +511,18 @@ def build_app(engine: AsyncLLMEngine, tokenizer, served_name: str, max_model_len
                         if isinstance(lps, BaseException):
                             yield f"data: {json.dumps({'error': str(lps)})}\n\n"
                             continue
+                        if reason == "__plp__":
+                            plps[k // n] = lps
+                            continue
                         lp = json.dumps(completion_logprobs(lps or [])) if want_lp else "null"
+                        extra = ""
+                        if not started[k] and req.prompt_logprobs is not None and k // n in plps:
+                            extra = ', "prompt_logprobs": ' + json.dumps(
+                                prompt_logprobs_json(plps[k // n], req.prompt_logprobs))
+                        started[k] = True
                         yield (f'{head}{int(time.time())}, "model": {model_js}, "choices": '
                                f'[{{"index": {k}, "text": {json.dumps(delta)}, "logprobs": '
-                               f'{lp}, "finish_reason": {json.dumps(reason)}}}]}}\n\n')
+                               f'{lp}, "finish_reason": {json.dumps(reason)}{extra}}}]}}\n\n')
                     yield "data: [DONE]\n\n"
                 finally:
                     for t in tasks:
@@ -453,11 +534,17 @@ def build_app(engine: AsyncLLMEngine, tokenizer, served_name: str, max_model_len
         finally:
             close_all(gens)
         choices = []
-        for k, (text, reason, _, lps) in enumerate(res):
+        for k, (text, reason, _, lps, _) in enumerate(res):
             pre = prefixes[k // n]
-            choices.append({"index": k, "text": pre + text,
-                            "logprobs": completion_logprobs(lps, len(pre)) if want_lp else None,
-                            "finish_reason": reason})
+            plp = res[k // n * n][4]                  # the prompt's choice 0 computed them
+            echo = (all_ids[k // n], plp) if req.echo else None
+            c = {"index": k, "text": pre + text,
+                 "logprobs": (completion_logprobs(lps, len(pre), echo, req.logprobs)
+                              if want_lp else None),
+                 "finish_reason": reason}
+            if req.prompt_logprobs is not None:
+                c["prompt_logprobs"] = prompt_logprobs_json(plp, req.prompt_logprobs)
+            choices.append(c)
         np_ = sum(len(ids) for ids in all_ids)
         nc = sum(r[2] for r in res)
         return JSONResponse({"id": rid, "object": "text_completion", "created": int(time.time()),
@@ -493,19 +580,26 @@ def build_app(engine: AsyncLLMEngine, tokenizer, served_name: str, max_model_len
         head = f'data: {{"id": "{rid}", "object": "text_completion", "created": '
         model_js = json.dumps(served_name)
 
-        def chunk(delta, reason, lps=None, index=0):
+        def chunk(delta, reason, lps=None, index=0, plp=None):
             """One SSE event; the constant head is formatted once per request."""
             lp = json.dumps(completion_logprobs(lps or [])) if want_lp else "null"
+            extra = ""
+            if plp is not None and req.prompt_logprobs is not None:
+                extra = ', "prompt_logprobs": ' + json.dumps(
+                    prompt_logprobs_json(plp, req.prompt_logprobs))
             return (f'{head}{int(time.time())}, "model": {model_js}, "choices": [{{"index": '
-                    f'{index}, "text": {json.dumps(delta)}, "logprobs": {lp}, "finish_reason": '
-                    f'{json.dumps(reason)}}}]}}\n\n')
+                    f'{index}, "text": {json.dumps(delta or "")}, "logprobs": {lp}, "finish_reason": '
+                    f'{json.dumps(reason)}{extra}}}]}}\n\n')
 
-        def final(text, reason, np_, nc, lps=None):
+        def final(text, reason, np_, nc, lps=None, plp=None):
+            c = {"index": 0, "text": prefix + text,
+                 "logprobs": completion_logprobs(lps, len(prefix), (ids, plp) if req.echo else None,
+                                                 req.logprobs or 0),
+                 "finish_reason": reason}
+            if req.prompt_logprobs is not None:
+                c["prompt_logprobs"] = prompt_logprobs_json(plp, req.prompt_logprobs)
             return {"id": rid, "object": "text_completion", "created": int(time.time()),
-                    "model": served_name,
-                    "choices": [{"index": 0, "text": prefix + text,
-                                 "logprobs": completion_logprobs(lps, len(prefix)),
-                                 "finish_reason": reason}],
+                    "model": served_name, "choices": [c],
                     "usage": {"prompt_tokens": np_, "completion_tokens": nc,
                               "total_tokens": np_ + nc}}
         try:
@@ -538,24 +632,27 @@ def build_app(engine: AsyncLLMEngine, tokenizer, served_name: str, max_model_len
         rid = f"chatcmpl-{uuid.uuid4().hex}"
         first = [True]
 
-        def chunk(delta, reason, lps=None, index=0):
-            d = {"content": delta}
+        def chunk(delta, reason, lps=None, index=0, plp=None):
+            d = {"content": delta or ""}
             if first[0]:
                 d["role"] = "assistant"
                 first[0] = False
             c = {"index": index, "delta": d, "finish_reason": reason}
             if req.logprobs:
                 c["logprobs"] = chat_logprobs(lps or [])
+            if plp is not None and req.prompt_logprobs is not None:
+                c["prompt_logprobs"] = prompt_logprobs_json(plp, req.prompt_logprobs)
             return "data: " + json.dumps({"id": rid, "object": "chat.completion.chunk",
                                           "created": int(time.time()), "model": served_name,
                                           "choices": [c]}) + "\n\n"
 
-        def final(text, reason, np_, nc, lps=None):
+        def final(text, reason, np_, nc, lps=None, plp=None):
+            c = {"index": 0, "message": {"role": "assistant", "content": text},
+                 "logprobs": chat_logprobs(lps), "finish_reason": reason}
+            if req.prompt_logprobs is not None:
+                c["prompt_logprobs"] = prompt_logprobs_json(plp, req.prompt_logprobs)
             return {"id": rid, "object": "chat.completion", "created": int(time.time()),
-                    "model": served_name,
-                    "choices": [{"index": 0, "message": {"role": "assistant", "content": text},
-                                 "logprobs": chat_logprobs(lps),
-                                 "finish_reason": reason}],
+                    "model": served_name, "choices": [c],
                     "usage": {"prompt_tokens": np_, "completion_tokens": nc,
                               "total_tokens": np_ + nc}}
         try:

@@ -32,6 +32,8 @@ def _merge(prev, nxt) -> None:
     nxt.new_token_ids = prev.new_token_ids + nxt.new_token_ids
     if prev.logprobs or nxt.logprobs:
         nxt.logprobs = (prev.logprobs or []) + (nxt.logprobs or [])
+    if getattr(prev, "prompt_logprobs", None) is not None:      # rides on the first token's output
+        nxt.prompt_logprobs = prev.prompt_logprobs
 
 
 class DoneLog:

@@ -248,7 +248,8 @@ def _core_main(cfg: EngineConfig, conn, listen: Optional[tuple] = None) -> None:
                     by_conn.setdefault(c, []).append(
                         (o.request_id, o.new_token_ids, o.finished, o.finish_reason,
                          o.arrival_time, o.first_token_time, o.finish_time,
-                         o.num_preemptions, o.logprobs))
+                         o.num_preemptions, o.logprobs,
+                         getattr(o, "prompt_logprobs", None)))
                 for c, items in by_conn.items():
                     try:
                         c.send(("out", items))
@@ -367,13 +368,13 @@ class EngineCoreClient:
                 kind = msg[0]
                 if kind == "out":
                     by_loop: dict = {}
-                    for rid, new, fin, reason, arr, ftt, ft, npre, lps in msg[1]:
+                    for rid, new, fin, reason, arr, ftt, ft, npre, lps, plp in msg[1]:
                         st = self._streams.get(rid) if not fin else self._streams.pop(rid, None)
                         if st is None:
                             continue
                         st.ids.extend(new)
                         o = RequestOutput(rid, st.prompt, new, st.ids, len(st.ids), fin, reason,
-                                          arr, ftt, ft, npre, lps)
+                                          arr, ftt, ft, npre, lps, plp)
                         by_loop.setdefault(st.loop, []).append((st.q, o))
                     for loop, items in by_loop.items():
                         loop.call_soon_threadsafe(_deliver, items)

@@ -441,6 +441,59 @@ def sample_vp_finish(packed: torch.Tensor, out: Optional[torch.Tensor] = None) -
     return out
 
 
+# ------------------------------------------------------------------ prompt logprobs (K15)
+MAX_PROMPT_LOGPROBS = 20
+
+
+def prompt_logprobs_partial(logits: torch.Tensor, targets: torch.Tensor, vocab_off: int = 0,
+                            ncols: Optional[int] = None, k: int = 0,
+                            splits: int = 0) -> torch.Tensor:
+    """K15 stage 1 over columns [0, ncols) of ``logits`` [R, Vloc] (a vocabulary shard
+    whose first global column is ``vocab_off``; rows may be strided and unaligned):
+    records [R, S, 3 + 2k] fp32 -- per column slice the max, sum exp(x - max), the logit
+    of ``targets`` [R] (global ids; -inf outside the slice) and the k best (value, global
+    id).  ``splits`` = 0: as many slices per row as the kernel chooses.  No [R, V]
+    intermediate is written."""
+    ncols = logits.shape[1] if ncols is None else ncols
+    if not 0 <= k <= MAX_PROMPT_LOGPROBS:
+        raise ValueError(f"k must be in 0..{MAX_PROMPT_LOGPROBS}")
+    if not _gpu(logits):
+        return ref.prompt_logprobs_partial(logits, targets, vocab_off, ncols, k, max(1, splits))
+    R = logits.shape[0]
+    S = splits or int(_k().plp_splits(R, ncols))
+    rec = torch.empty(R, S, 3 + 2 * k, dtype=torch.float32, device=logits.device)
+    _k().plp_partial(rec, logits, targets, vocab_off, ncols, k)
+    return rec
+
+
+def prompt_logprobs_merge(rec: torch.Tensor, k: int, as_record: bool = False):
+    """K15 stage 2: the records of each row (``rec`` [R, N, 3 + 2k]: the slices of one
+    rank, or the per-rank records after an all-gather) -> (token logprob [R] fp32, top
+    logprobs [R, k] fp32, top ids [R, k] int32, best first, (-inf, -1) padded);
+    ``as_record``: one merged record [R, 3 + 2k] per row instead."""
+    if not _gpu(rec):
+        return ref.prompt_logprobs_merge(rec, k, as_record)
+    R = rec.shape[0]
+    rec = rec.contiguous()
+    if as_record:
+        out = torch.empty(R, 3 + 2 * k, dtype=torch.float32, device=rec.device)
+        e = out[:0]
+        _k().plp_merge(e, e, e.view(torch.int32), out, rec, k)
+        return out
+    tok = torch.empty(R, dtype=torch.float32, device=rec.device)
+    top = torch.empty(R, k, dtype=torch.float32, device=rec.device)
+    ids = torch.empty(R, k, dtype=torch.int32, device=rec.device)
+    _k().plp_merge(tok, top, ids, None, rec, k)
+    return tok, top, ids
+
+
+def prompt_logprobs(logits: torch.Tensor, targets: torch.Tensor, k: int = 0, vocab_off: int = 0,
+                    ncols: Optional[int] = None):
+    """log-softmax value of ``targets`` and the k best columns of each row of ``logits``
+    (one rank holding the whole vocabulary): stage 1 then stage 2."""
+    return prompt_logprobs_merge(prompt_logprobs_partial(logits, targets, vocab_off, ncols, k), k)
+
+
 __all__ = ["load_extension", "rms_norm", "fused_add_rms_norm", "layer_norm", "silu_mul",
            "rope_kv_write", "paged_attention_decode", "paged_attention_decode_rope", "prefill_attention", "sample", "sample_vp_partial", "sample_vp_finish",
            "decode_partials", "decode_grid_z", "moe_pack", "moe_packable", "prefill_work_list", "ref"]

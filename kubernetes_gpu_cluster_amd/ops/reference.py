@@ -317,6 +317,100 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor,
     return out.to(logits.device)
 
 
+# ---------------------------------------------------------------- K15 prompt logprobs
+_NEG_INF = float("-inf")
+
+
+def _plp_best(vals: torch.Tensor, ids: torch.Tensor, k: int):
+    """The k best (value, id) per row of vals / ids [R, C]: value descending as floats
+    (-0.0 == +0.0), equal values by ascending id; id -1 marks padding (always last).
+    Two stable sorts realise the tie rule (``torch.topk`` promises none).  Fewer than k
+    valid entries: the tail is (-inf, -1)."""
+    R, C = vals.shape
+    out_v = torch.full((R, k), _NEG_INF, dtype=torch.float32)
+    out_i = torch.full((R, k), -1, dtype=torch.int32)
+    if k == 0 or C == 0:
+        return out_v, out_i
+    ids = ids.to(torch.int64)
+    v1, i1 = vals, ids
+    if C > 1 and not bool(((ids[:, 1:] > ids[:, :-1]) & (ids[:, :-1] >= 0)).all()):
+        by_id = torch.sort(torch.where(ids < 0, torch.full_like(ids, 1 << 40), ids), dim=1,
+                           stable=True).indices
+        v1, i1 = vals.gather(1, by_id), ids.gather(1, by_id)
+    key = torch.where(i1 < 0, torch.full_like(v1, _NEG_INF), v1) + 0.0     # -0.0 -> +0.0
+    # padding ties with real -inf columns; it is behind them already (sorted by id)
+    by_v = torch.sort(key, dim=1, descending=True, stable=True).indices[:, :k]
+    n = by_v.shape[1]
+    out_v[:, :n] = v1.gather(1, by_v)
+    out_i[:, :n] = i1.gather(1, by_v).to(torch.int32)
+    out_v[out_i < 0] = _NEG_INF
+    return out_v, out_i
+
+
+def prompt_logprobs_partial(logits: torch.Tensor, targets: torch.Tensor, vocab_off: int,
+                            ncols: int, k: int, splits: int = 1) -> torch.Tensor:
+    """K15 stage 1: records [R, splits, 3 + 2k] fp32 over columns [0, ncols) of the shard
+    ``logits`` (global column = vocab_off + local): per slice the max m, s = sum exp(x - m),
+    the target's logit t (-inf when the target is not in the slice), and the slice's k best
+    (value, global id) -- ids stored as int32 bit patterns in the fp32 words."""
+    R = logits.shape[0]
+    rec = torch.empty(R, splits, 3 + 2 * k, dtype=torch.float32)
+    x = logits[:, :ncols].float().cpu()
+    tg = targets.cpu().to(torch.int64)
+    for y in range(splits):
+        lo, hi = ncols * y // splits, ncols * (y + 1) // splits
+        xs = x[:, lo:hi]
+        n = hi - lo
+        if n:
+            m = xs.max(dim=1).values
+            ms = torch.where(m == _NEG_INF, torch.zeros_like(m), m)
+            s = torch.exp(xs - ms[:, None]).sum(dim=1)
+            tl = tg - vocab_off - lo
+            inside = (tl >= 0) & (tl < n)
+            t = torch.where(inside, xs.gather(1, tl.clamp(0, n - 1)[:, None])[:, 0],
+                            torch.full_like(m, _NEG_INF))
+        else:
+            m = torch.full((R,), _NEG_INF)
+            s, t = torch.zeros(R), m.clone()
+        rec[:, y, 0], rec[:, y, 1], rec[:, y, 2] = m, s, t
+        ids = torch.arange(vocab_off + lo, vocab_off + hi, dtype=torch.int64).expand(R, n)
+        v, i = _plp_best(xs, ids, k)
+        rec[:, y, 3:3 + k] = v
+        rec.view(torch.int32)[:, y, 3 + k:] = i          # bit patterns, not values
+    return rec.to(logits.device)
+
+
+def prompt_logprobs_merge(rec: torch.Tensor, k: int, as_record: bool = False):
+    """K15 stage 2: the N records of each row (``rec`` [R, N, 3 + 2k]) -> (token logprob
+    [R], top logprobs [R, k], top ids int32 [R, k]); ``as_record``: one merged record
+    [R, 3 + 2k] instead (what a TP rank all-gathers).  Empty records (m = -inf, s = 0) add
+    nothing; -inf values stay -inf."""
+    dev = rec.device
+    rec = rec.cpu()
+    R, N, _ = rec.shape
+    m, s, t = rec[:, :, 0], rec[:, :, 1], rec[:, :, 2]
+    M = m.max(dim=1).values
+    Ms = torch.where(M == _NEG_INF, torch.zeros_like(M), M)
+    S = (s * torch.exp(m - Ms[:, None])).sum(dim=1)
+    T = t.max(dim=1).values
+    vals = rec[:, :, 3:3 + k].reshape(R, N * k)
+    ids = rec[:, :, 3 + k:].contiguous().view(torch.int32).reshape(R, N * k)
+    v, i = _plp_best(vals, ids, k)
+    if as_record:
+        out = torch.empty(R, 3 + 2 * k, dtype=torch.float32)
+        out[:, 0], out[:, 1], out[:, 2] = M, S, T
+        out[:, 3:3 + k] = v
+        out.view(torch.int32)[:, 3 + k:] = i
+        return out.to(dev)
+    lse = Ms + torch.log(S)
+
+    def lp(x):
+        dead = (x == _NEG_INF) | ~(S > 0).reshape([-1] + [1] * (x.dim() - 1)).expand_as(x)
+        return torch.where(dead, torch.full_like(x, _NEG_INF),
+                           x - lse.reshape([-1] + [1] * (x.dim() - 1)))
+    return lp(T).to(dev), lp(v).to(dev), i.to(dev)
+
+
 # ---------------------------------------------------------------- MoE
 def moe_topk_softmax(router_logits: torch.Tensor, k: int, renormalize: bool = True):
     """K13: softmax over experts, top-k; returns (weights fp32 [T,k], ids int32 [T,k])."""
