@@ -833,24 +833,15 @@ class ModelRunner:
                              tail_shapes=getattr(self.model, "tail_shapes", lambda: set())(),
                              qkv_dims=getattr(self.model, "qkv_dims", lambda: {})(),
                              rs_shapes=getattr(self.model, "_rs_w", None) is not None)
-            method = getattr(self.model, "quantization", None)
-            if method == "fp8":
-                # --quantization fp8: K9q's (M <= 64) and K9mq's (M > 64) configurations
-                # against the widen path, per bucket
+            q = gemm.QUANT_METHODS.get(getattr(self.model, "quantization", None))
+            if q is not None:
+                # --quantization fp8 / mxfp4: K9q's / K9f's (M <= 64) and K9mq's / K9mf's
+                # (M > 64) configurations against the widen path, per bucket
                 from ..models.quant import dense_projections
-                gu = {tuple(l.mlp.gate_up_proj.weight.shape) for l in self.model.layers}
-                gemm.tune_w8([m.weight for l in self.model.layers for m in dense_projections(l)],
-                             self.buckets, self.dtype, silu_shapes=gu,
-                             tail_shapes=getattr(self.model, "w8_tail_shapes", lambda: set())())
-            elif method == "mxfp4":
-                # --quantization mxfp4: K9f's (M <= 64) and K9mf's (M > 64) configurations
-                # against the widen path, per bucket; the stored weight is [N, K/2] bytes
-                from ..models.quant import dense_projections
-                gu = {(l.mlp.gate_up_proj.weight.shape[0], 2 * l.mlp.gate_up_proj.weight.shape[1])
-                      for l in self.model.layers}
-                gemm.tune_w4([m.weight for l in self.model.layers for m in dense_projections(l)],
-                             self.buckets, self.dtype, silu_shapes=gu,
-                             tail_shapes=getattr(self.model, "w4_tail_shapes", lambda: set())())
+                gu = {q.nk(l.mlp.gate_up_proj.weight) for l in self.model.layers}
+                q.tune([m.weight for l in self.model.layers for m in dense_projections(l)],
+                       self.buckets, self.dtype, silu_shapes=gu,
+                       tail_shapes=getattr(self.model, "quant_tail_shapes", lambda: set())())
         whole = self.model.first and self.model.last
         if (not self.use_graphs or not (whole or self.pp_link is not None)
                 or not getattr(self.model, "graph_safe", True)):

@@ -141,12 +141,12 @@ class Worker:
                 from ..ops import gemm
                 gu = [l.mlp.gate_up_proj.weight for l in self.model.layers]
                 skip = {id(w) for w in gu}
-                pack, kname = ((gemm.pack_w8_decode_weights, "K9mq") if cfg.quantization == "fp8"
-                               else (gemm.pack_w4_decode_weights, "K9mf"))
-                nb = pack([m.weight for l in self.model.layers for m in dense_projections(l)
-                           if id(m.weight) not in skip], gu)
+                q = gemm.QUANT_METHODS[cfg.quantization]
+                nb = q.pack_decode_weights([m.weight for l in self.model.layers
+                                            for m in dense_projections(l)
+                                            if id(m.weight) not in skip], gu)
                 log.info("quantization %s: %.2f GB (%d bytes) of packed %s weight copies",
-                         cfg.quantization, nb / 1e9, nb, kname)
+                         cfg.quantization, nb / 1e9, nb, q.mid)
         if dev.type == "cuda" and not cfg.enforce_eager:
             # packed copies of the decode-GEMM weights for the K9m tiles, made before the
             # KV cache is sized so the pool accounts for them (ops/gemm.py)

@@ -498,25 +498,17 @@ class LlamaForCausalLM(nn.Module):
             return {tuple(l0.self_attn.o_proj.weight.shape)}
         return {tuple(l0.self_attn.o_proj.weight.shape), tuple(l0.mlp.down_proj.weight.shape)}
 
-    def w8_tail_shapes(self) -> set:
-        """``tail_shapes`` of an fp8 model: the o / down projections whose K9mq split-K
-        reduction the following residual add + RMSNorm absorbs (ops/gemm.py tune_w8)."""
-        if not (self.first and self.last and self.layers and self.quantization == "fp8"
+    def quant_tail_shapes(self) -> set:
+        """``tail_shapes`` of a quantised model, as (N, K) of the layer: the o / down
+        projections whose K9mq / K9mf split-K reduction the following residual add + RMSNorm
+        absorbs (ops/gemm.py QuantMethod.tune)."""
+        from ..ops import gemm
+        q = gemm.QUANT_METHODS.get(self.quantization)
+        if not (self.first and self.last and self.layers and q is not None
                 and get_state().tp_size == 1 and _tail_fusion_enabled and not self.cfg.is_moe):
             return set()
         l0 = self.layers[0]
-        return {tuple(l0.self_attn.o_proj.weight.shape), tuple(l0.mlp.down_proj.weight.shape)}
-
-    def w4_tail_shapes(self) -> set:
-        """``w8_tail_shapes`` of an mxfp4 model, as (N, K) of the layer (the stored codes are
-        [N, K/2] bytes): the o / down projections whose K9mf split-K reduction the following
-        residual add + RMSNorm absorbs (ops/gemm.py tune_w4)."""
-        if not (self.first and self.last and self.layers and self.quantization == "mxfp4"
-                and get_state().tp_size == 1 and _tail_fusion_enabled and not self.cfg.is_moe):
-            return set()
-        l0 = self.layers[0]
-        return {(w.shape[0], 2 * w.shape[1])
-                for w in (l0.self_attn.o_proj.weight, l0.mlp.down_proj.weight)}
+        return {q.nk(l0.self_attn.o_proj.weight), q.nk(l0.mlp.down_proj.weight)}
 
     def fused_norm_shapes(self) -> set:
         """(N, K) of the GEMMs whose input RMSNorm the fused layer absorbs (tuned at start)."""

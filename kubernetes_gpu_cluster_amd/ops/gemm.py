@@ -17,10 +17,15 @@ import logging
 import os
 import time
 import weakref
-from typing import Iterable, Optional
+from dataclasses import dataclass
+from functools import partial
+from typing import Callable, Iterable, Optional
 
 import torch
 import torch.nn.functional as F
+
+from .quant import (MXFP4_TILE_BYTES, dequantize_fp8_rows, dequantize_mxfp4, is_fp8, is_mxfp4,
+                    tile_rows, w4_scale, w8_scale)
 
 log = logging.getLogger("kgc.gemm")
 
@@ -61,14 +66,16 @@ _enabled = os.environ.get("KGC_SKINNY_GEMM", "1") != "0"
 DG_MAX_M = 512
 _plan_dg: dict[tuple[int, int, int, str], tuple[int, int]] = {}
 _dg_enabled = os.environ.get("KGC_DGEMM", "1") != "0"
-# packed weight copies for the packed K9m tiles: (data_ptr, silu) -> [N/128, K/64, 8192]
-# (data_ptr, silu) -> (weakref to the source weight, packed copy).  The weakref drops the
-# entry when the weight dies: a later tensor allocated at the same address (the next
-# engine in the same process, a test) must never pick up this weight's packed copy.
+# packed weight copies -- K9m's bf16 tiles [N/128, K/64, 8192], K9mq's e4m3 tiles, K9mf's
+# mxfp4 tiles: (data_ptr, silu) -> (weakref to the source weight, packed copy, extra); extra,
+# fp8 silu only: the row scales in the packed tiles' row order, for the split-K slices.  The
+# weakref drops the entry when the weight dies: a later tensor allocated at the same address
+# (the next engine in the same process, a test) must never pick up this weight's packed copy.
 _packed: dict[tuple[int, bool], tuple] = {}
 
 
-def _packed_get(w: torch.Tensor, silu: bool) -> Optional[torch.Tensor]:
+def _packed_entry(w: torch.Tensor, silu: bool) -> Optional[tuple]:
+    """The registry entry (weakref, packed copy, extra) of ``w``, or None."""
     key = (w.data_ptr(), silu)
     e = _packed.get(key)
     if e is None:
@@ -77,54 +84,399 @@ def _packed_get(w: torch.Tensor, silu: bool) -> Optional[torch.Tensor]:
     if src is None:
         _packed.pop(key, None)
         return None
-    if src.data_ptr() != w.data_ptr() or src.shape != w.shape:
+    if src.data_ptr() != w.data_ptr() or src.shape != w.shape or src.dtype != w.dtype:
         return None
-    return e[1]
+    return e
 
 
-def _packed_put(w: torch.Tensor, silu: bool, p: torch.Tensor) -> None:
+def _packed_get(w: torch.Tensor, silu: bool = False) -> Optional[torch.Tensor]:
+    e = _packed_entry(w, silu)
+    return None if e is None else e[1]
+
+
+def _packed_put(w: torch.Tensor, silu: bool, p: torch.Tensor, extra=None) -> None:
     key = (w.data_ptr(), silu)
 
     def drop(ref, key=key):
         e = _packed.get(key)
         if e is not None and e[0] is ref:
             del _packed[key]
-    _packed[key] = (weakref.ref(w, drop), p)
+    _packed[key] = (weakref.ref(w, drop), p, extra)
+
+
 _PACK_FRACTION = float(os.environ.get("KGC_DGEMM_PACK_FRACTION", "0.25"))
 
 
-# ------------------------------------------------------------------ W8A16 (--quantization fp8)
-# fp8 weights (ops/quant.py) never meet the bf16 plans above, which are keyed by (M, N, K)
-# only: every entry point below checks the weight's dtype first.
-#   M <= 64: K9q (csrc/kernels/gemm_w8.hip), or -- where start-up timing measured it faster,
-#            or no K9q configuration fits the shape -- the widen path;
-#   M  > 64: the widen path: kgc.w8_widen writes round(w8 * scale) into a static per-device
-#            scratch and the library GEMM runs on it (correct and graph-capturable, but it
-#            moves MORE bytes than a bf16 weight would: 1 read + 2 written + 2 read per
-#            element) -- except at the decode buckets with 64 < M <= 512 where the plan
-#            below names a K9mq configuration (csrc/kernels/gemm_w8_decode.hip: the K9m
-#            pipeline streaming packed e4m3 tiles, one byte per weight element).
-# (M, N, K) -> K9q cfg, or None where the widen path measured faster
-_plan_w8: dict[tuple[int, int, int], Optional[tuple]] = {}
-# merged gate_up (M, 2I, K) -> cfg of K9q's SiLU form, where it beat the plan + silu_mul
-_plan_w8_silu: dict[tuple[int, int, int], Optional[tuple]] = {}
-_w8_scratch: dict[tuple, torch.Tensor] = {}
-_w8_scratch_old: list = []      # outgrown scratches stay alive: captured graphs write them
-_w8_counts = {"k9q": 0, "k9q_silu": 0, "widen": 0, "k9mq": 0, "k9mq_silu": 0}
-_w8_enabled = os.environ.get("KGC_W8_GEMM", "1") != "0"
-# K9mq: (M, N, K, kind) -> (cfg, S), or None where the widen path (with the same consumer)
-# measured faster; kind as in _plan_dg ("plain" | "silu" | "tail").  No entry: widen.
-_plan_w8_dg: dict[tuple[int, int, int, str], Optional[tuple[int, int]]] = {}
-# KGC_W8_DGEMM: "1" tuned (default), "0" off (nothing packed, the widen path runs), "force"
-# (no timing: the first configuration in table order that fits, S = 1 -- tests, A/B runs)
-w8_dgemm_mode = os.environ.get("KGC_W8_DGEMM", "1")
-# packed copies of quantised weights (K9mq's e4m3 tiles, K9mf's mxfp4 tiles): (data_ptr, silu)
-# -> (weakref to the weight, packed tiles, extra); extra, fp8 silu only: the row scales in
-# the packed tiles' row order, for the split-K slices.  The weakref drops the entry when the
-# weight dies, as in _packed
-_q_packed: dict[tuple[int, bool], tuple] = {}
+# ------------------------------------------------- W8A16 / W4A16 (--quantization fp8 | mxfp4)
+# Quantised weights (ops/quant.py) never meet the bf16 plans above, which are keyed by
+# (M, N, K) only: every entry point below checks the weight's dtype first.  An fp8 weight is
+# e4m3 [N, K] carrying one fp32 scale per row; an mxfp4 weight is uint8 codes [N, K/2]
+# carrying its e8m0 block scales [N, K/32] (``QuantMethod.nk`` is the only place that knows).
+# Both methods route alike, each over its own kernel family:
+#   M <= 64: K9q (csrc/kernels/gemm_w8.hip) / K9f (csrc/kernels/gemm_w4.hip), or -- where
+#            start-up timing measured it faster, or no configuration fits the shape -- the
+#            widen path;
+#   M  > 64, prefill: the widen path: kgc.w8_widen writes round(w8 * scale), kgc.w4_widen the
+#            exact dequantised weight, into a static scratch (one per device and dtype, shared
+#            by both methods) and the library GEMM runs on it (correct and graph-capturable,
+#            but it moves MORE bytes than a bf16 weight would: 1 (or 0.53) read + 2 written +
+#            2 read per element) -- except at the decode buckets with 64 < M <= 512 where the
+#            mid-M plan names a K9mq (csrc/kernels/gemm_w8_decode.hip) / K9mf
+#            (csrc/kernels/gemm_w4_decode.hip) configuration: the K9m pipeline streaming
+#            packed e4m3 tiles (one byte per weight element) or packed mxfp4 tiles (0.53).
+# Everything that differs between the two is a ``QuantMethod`` instance (W8, W4 below); the
+# routing, the tuners and the packing are written once, as its methods.
+_U8 = torch.uint8               # a --quantization mxfp4 weight's codes
+_q_scratch: dict[tuple, torch.Tensor] = {}
+_q_scratch_old: list = []       # outgrown scratches stay alive: captured graphs write them
+
+
+def _kgc():
+    from . import _k
+    return _k()
+
+
+def w8_reserve(device: torch.device, numel: int, dtype: torch.dtype) -> torch.Tensor:
+    """The widen path's scratch on ``device``: at least ``numel`` elements of ``dtype``.
+    The engine reserves the largest quantised weight before graphs are captured."""
+    key = (device, dtype)
+    s = _q_scratch.get(key)
+    if s is None or s.numel() < numel:
+        if s is not None:
+            _q_scratch_old.append(s)
+        s = _q_scratch[key] = torch.empty(numel, dtype=dtype, device=device)
+    return s
+
+
+def _q_x_ok(x: torch.Tensor) -> bool:
+    return (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 8 == 0
+            and x.data_ptr() % 16 == 0 and x.dtype in (torch.bfloat16, torch.float16))
+
+
+def q_dg_ok(M: int, N: int, K: int, cfg: int = 0, S: int = 1) -> bool:
+    """Shapes K9mq and K9mf take (K the layer's, not the code bytes): 64 < M <= 512, N in
+    whole 128-column tiles, K in whole 64-k steps, at most one K-slice per step (and the 32
+    slices the bindings allow)."""
+    return (SKINNY_MAX_M < M <= DG_MAX_M and N >= 128 and N % 128 == 0 and K >= 64
+            and K % 64 == 0 and cfg >= 0 and 1 <= S <= min(32, K // 64))
+
+
+@dataclass(eq=False)
+class QuantMethod:
+    """One weight-only quantisation method: what differs between fp8 and mxfp4 as fields,
+    what they share as methods.  ``ops/gemm.py`` binds the methods of the two instances to
+    the module's ``w8_*`` / ``w4_*`` names."""
+    method: str                 # the --quantization value
+    tag: str                    # "W8" / "W4": log lines, KGC_<tag>_GEMM, KGC_<tag>_DGEMM
+    sk: str                     # the M <= 64 kernel, K9q / K9f (lower case: its counter keys)
+    mid: str                    # the 64 < M <= 512 kernel, K9mq / K9mf
+    configs: list               # the small-M kernel's configurations, in the tuner's order
+    ok: Callable                # (M, N, K, cfg): the small-M kernel takes the shape
+    default_cfg: Callable       # (M, N, K, silu=False): the configuration without a plan
+    is_weight: Callable         # (w): a weight of this method
+    nk: Callable                # (w) -> (N, K) of the layer
+    scale: Callable             # (w) -> the scales the weight carries
+    dequant: Callable           # (w, scale, dtype): the CPU path's weight
+    tile_bytes: int             # one packed [128 rows x 64 k] tile of the mid-M kernel
+    # the bindings: (out, x, w, scale, bias, *cfg, silu); (out, w, scale);
+    # (out, x, w, registry entry, bias, cfg, epi); (packed, w, silu) -> the entry's extra;
+    # () -> the mid-M kernel's (BM, BN, ring slots) per configuration id
+    op_gemm: Callable
+    op_widen: Callable
+    op_mid: Callable
+    op_pack: Callable
+    op_tiles: Callable
+
+    def __post_init__(self):
+        # KGC_W8_GEMM / KGC_W4_GEMM=0: the small-M kernel off, nothing packed or tuned
+        self.enabled = os.environ.get(f"KGC_{self.tag}_GEMM", "1") != "0"
+        # KGC_W8_DGEMM / KGC_W4_DGEMM: "1" tuned (default), "0" off (nothing packed, the widen
+        # path runs), "force" (no timing: the first configuration in table order that fits,
+        # S = 1 -- tests, A/B runs)
+        self.dgemm_mode = os.environ.get(f"KGC_{self.tag}_DGEMM", "1")
+        # (M, N, K) -> small-M cfg, or None where the widen path measured faster
+        self.plan: dict[tuple[int, int, int], Optional[tuple]] = {}
+        # merged gate_up (M, 2I, K) -> cfg of the SiLU form, where it beat the plan + silu_mul
+        self.plan_silu: dict[tuple[int, int, int], Optional[tuple]] = {}
+        # (M, N, K, kind) -> mid-M (cfg, S), or None where the widen path (with the same
+        # consumer) measured faster; kind as in _plan_dg ("plain" | "silu" | "tail").  No
+        # entry: widen.
+        self.plan_dg: dict[tuple[int, int, int, str], Optional[tuple[int, int]]] = {}
+        self.k_sk, self.k_mid = self.sk.lower(), self.mid.lower()
+        self.counts = {self.k_sk: 0, self.k_sk + "_silu": 0, "widen": 0,
+                       self.k_mid: 0, self.k_mid + "_silu": 0}
+        self._tiles: list = []      # (BM, BN, ring slots) per configuration id, read once
+
+    # -------------------------------------------------------------- launches
+    def gemm(self, x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor,
+             bias: Optional[torch.Tensor], cfg, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """K9q / K9f: x dq(W)^T (+ bias) in x's dtype."""
+        if out is None:
+            out = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
+        self.op_gemm(out, x, w, scale, bias, *cfg, False)
+        self.counts[self.k_sk] += 1
+        return out
+
+    def silu(self, x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor, cfg,
+             out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """K9q's / K9f's SiLU form over a merged [gate; up] weight [2I, K]: out [M, I]."""
+        if out is None:
+            out = torch.empty(x.shape[0], w.shape[0] // 2, dtype=x.dtype, device=x.device)
+        self.op_gemm(out, x, w, scale, None, *cfg, True)
+        self.counts[self.k_sk + "_silu"] += 1
+        return out
+
+    def widen(self, w: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+        """The dequantised weight as a [N, K] view of the device's scratch (the one
+        ``w8_reserve`` keeps; valid until the next widen of either method)."""
+        N, K = self.nk(w)
+        out = w8_reserve(w.device, N * K, dtype)[: N * K].view(N, K)
+        self.op_widen(out, w, scale)
+        return out
+
+    def widen_linear(self, x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor,
+                     bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self.counts["widen"] += 1
+        return F.linear(x, self.widen(w, scale, x.dtype), bias)
+
+    def tiles(self) -> list:
+        if not self._tiles:
+            self._tiles.extend(tuple(int(v) for v in t) for t in self.op_tiles())
+        return self._tiles
+
+    def dgemm(self, x: torch.Tensor, w: torch.Tensor, cfg: int, S: int, epi: int = 1,
+              out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
+              silu_w: bool = False) -> torch.Tensor:
+        """K9mq / K9mf over ``w``'s packed copy: S == 1 -> x dq(W)^T (+ bias) in x's dtype
+        (epi 1) or the SiLU pairs [M, N/2] of a merged gate_up weight (epi 2); S > 1 -> the
+        [S, M, N] fp32 K-slices, each already scaled (the caller's consumer sums them).
+        silu_w: slices of the SiLU-packed copy (``splitk_reduce_silu(interleaved=True)``)."""
+        silu = epi == 2 or silu_w
+        e = _packed_entry(w, silu)
+        if e is None:
+            raise RuntimeError(f"{self.mid}: the weight has no packed copy "
+                               f"(pack_{self.tag.lower()}_decode_weights)")
+        M, N = x.shape[0], w.shape[0]
+        if S > 1:
+            if bias is not None:
+                raise RuntimeError(f"{self.mid}: no bias on split-K slices")
+            out = torch.empty(S, M, N, dtype=torch.float32, device=x.device) if out is None else out
+            self.op_mid(out, x, w, e, None, cfg, 0)
+        else:
+            if out is None:
+                out = torch.empty(M, N // 2 if epi == 2 else N, dtype=x.dtype, device=x.device)
+            self.op_mid(out, x, w, e, bias, cfg, epi)
+        self.counts[self.k_mid + "_silu" if silu else self.k_mid] += 1
+        return out
+
+    # -------------------------------------------------------------- routing
+    def _dg_plan(self, x: torch.Tensor, w: torch.Tensor, kind: str):
+        """The mid-M (cfg, S) of this call, or None: no entry, a None entry, the knob off, an X
+        the kernel does not take, or a weight without its packed copy -> the widen path."""
+        if not self.plan_dg or self.dgemm_mode == "0" or not x.is_cuda or not _q_x_ok(x):
+            return None
+        p = self.plan_dg.get((x.shape[0], *self.nk(w), kind))
+        if p is None or _packed_get(w, kind == "silu") is None:
+            return None
+        return p
+
+    def linear(self, x: torch.Tensor, w: torch.Tensor,
+               bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A quantised linear layer.  CPU (the oracle, and what the CPU suite runs): F.linear
+        on the dequantised weight in the activation dtype."""
+        scale = self.scale(w)
+        if not x.is_cuda:
+            return F.linear(x, self.dequant(w, scale, x.dtype), bias)
+        N, K = self.nk(w)
+        if x.dim() != 2:
+            return self.linear(x.reshape(-1, x.shape[-1]), w, bias).view(*x.shape[:-1], N)
+        M = x.shape[0]
+        if self.enabled and 1 <= M <= SKINNY_MAX_M and _q_x_ok(x):
+            key = (M, N, K)
+            cfg = self.plan[key] if key in self.plan else self.default_cfg(M, N, K)
+            if cfg is not None:
+                return self.gemm(x, w, scale, bias, cfg)
+        p = self._dg_plan(x, w, "plain")
+        if p is not None and (p[1] == 1 or bias is None):
+            cfg, S = p
+            if S == 1:
+                return self.dgemm(x, w, cfg, 1, bias=bias)
+            out = torch.empty(M, N, dtype=x.dtype, device=x.device)
+            _kgc().splitk_reduce(out, self.dgemm(x, w, cfg, S))
+            return out
+        return self.widen_linear(x, w, scale, bias)
+
+    def linear_silu(self, x: torch.Tensor, w: torch.Tensor,
+                    bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        from . import silu_mul
+        if (self.enabled and bias is None and x.is_cuda and _q_x_ok(x)
+                and 1 <= x.shape[0] <= SKINNY_MAX_M):
+            key = (x.shape[0], *self.nk(w))
+            cfg = (self.plan_silu[key] if key in self.plan_silu
+                   else self.default_cfg(*key, silu=True))
+            if cfg is not None:
+                return self.silu(x, w, self.scale(w), cfg)
+        p = self._dg_plan(x, w, "silu") if bias is None and x.is_cuda else None
+        if p is not None:
+            cfg, S = p
+            if S == 1:
+                return self.dgemm(x, w, cfg, 1, epi=2)
+            out = torch.empty(x.shape[0], w.shape[0] // 2, dtype=x.dtype, device=x.device)
+            _kgc().splitk_reduce_silu(out, self.dgemm(x, w, cfg, S, silu_w=True), True)
+            return out
+        return silu_mul(self.linear(x, w, bias))
+
+    def linear_add_rms(self, x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor,
+                       gamma: torch.Tensor, eps: float) -> tuple[torch.Tensor, torch.Tensor]:
+        """``linear_add_rms`` over a quantised o / down projection."""
+        from . import fused_add_rms_norm
+        p = self._dg_plan(x, w, "tail") if x.is_cuda else None
+        if p is not None and w.shape[0] <= 8192 and residual.is_contiguous():
+            cfg, S = p
+            if S > 1:
+                out = torch.empty_like(residual)
+                _kgc().splitk_add_rms_norm(out, self.dgemm(x, w, cfg, S), residual, gamma, eps)
+                return out, residual
+            return fused_add_rms_norm(self.dgemm(x, w, cfg, 1), residual, gamma, eps)
+        return fused_add_rms_norm(self.linear(x, w), residual, gamma, eps)
+
+    # -------------------------------------------------------------- packing and tuning
+    def pack_decode_weights(self, plain: Iterable[torch.Tensor],
+                            silu: Iterable[torch.Tensor]) -> int:
+        """Packed copies ([N/128][K/64] tiles of ``tile_bytes``: ``quant.pack_fp8_tiles_reference``
+        / ``quant.pack_mxfp4_tiles_reference``) of a quantised model's decode-GEMM weights for
+        K9mq / K9mf, made once before the KV cache is sized.  ``silu``: merged gate_up weights,
+        packed with gate and up 16-row groups interleaved.  Nothing is packed (the widen path
+        stays) with KGC_W8_DGEMM / KGC_W4_DGEMM=0 or when the copies would exceed
+        KGC_DGEMM_PACK_FRACTION of device memory.  Returns bytes packed."""
+        if self.dgemm_mode == "0" or not self.enabled:
+            return 0
+        todo, need = [], 0
+        for w, sl in [(w, False) for w in plain] + [(w, True) for w in silu]:
+            if not (w.is_cuda and w.dim() == 2 and self.is_weight(w) and w.is_contiguous()):
+                continue
+            N, K = self.nk(w)
+            if (N % 128 == 0 and K % 64 == 0 and (not sl or (N // 2) % 64 == 0)
+                    and _packed_get(w, sl) is None):
+                todo.append((w, sl, N // 128, K // 64))
+                need += N // 128 * (K // 64) * self.tile_bytes
+        if not todo:
+            return 0
+        free, total = torch.cuda.mem_get_info(todo[0][0].device)
+        if need > _PACK_FRACTION * total or need > free - (8 << 30):
+            log.info("%s: %.1f GB of packed %s weights exceeds the budget; widen path only",
+                     self.mid, need / 1e9, self.method)
+            return 0
+        for w, sl, nb, kb in todo:
+            p = torch.empty(nb, kb, self.tile_bytes, dtype=w.dtype, device=w.device)
+            _packed_put(w, sl, p, self.op_pack(p, w, sl))
+        log.info("%s: packed %d %s decode weights (%.2f GB, out of the KV pool; "
+                 "KGC_%s_DGEMM=0 returns them)", self.mid, len(todo), self.method, need / 1e9,
+                 self.tag)
+        return need
+
+    def _tune_dgemm(self, ws, N: int, K: int, ms, dtype, reps: int, res: dict, kind: str) -> None:
+        """``_tune_q_dgemm`` for K9mq / K9mf over the weights ``ws`` of one shape (all packed,
+        or nothing is tuned: the tuner never packs).  Mode "force": no timing."""
+        silu = kind == "silu"
+        es = [_packed_entry(w, silu) for w in ws]
+        if any(e is None for e in es):
+            return
+        sc = [self.scale(w) for w in ws]
+        _tune_q_dgemm(len(ws), ws[0].device, N, K, ms, dtype, reps, res, kind, tag=self.tag,
+                      kname=self.mid, mode=self.dgemm_mode, plan=self.plan_dg, tiles=self.tiles(),
+                      wide_linear=lambda x, i: self.widen_linear(x, ws[i], sc[i]),
+                      launch=lambda buf, x, i, cfg, epi: self.op_mid(buf, x, ws[i], es[i], None,
+                                                                     cfg, epi))
+
+    @torch.inference_mode()
+    def tune(self, weights: Iterable[torch.Tensor], ms: Iterable[int], dtype: torch.dtype,
+             silu_shapes=(), reps: int = 3, tail_shapes=()) -> dict:
+        """For each weight shape of this method and decode bucket M <= 64: every K9q / K9f
+        configuration against the widen path, graph-replayed over ALL weights of the shape
+        (HBM-resident, as in a decode step); the faster goes into ``plan``.  ``silu_shapes``:
+        (N, K) of merged gate_up weights, whose SiLU form is timed against the plain winner +
+        silu_mul.  Decode buckets with 64 < M <= 512: the K9mq / K9mf candidates against the
+        widen path, each with its consumer (``_tune_dgemm``; ``tail_shapes``: (N, K) of the
+        o / down projections that feed ``linear_add_rms``), only for the weights
+        ``pack_decode_weights`` packed -- the results go into ``plan_dg``, never into
+        ``plan``.  Returns {(M, N, K): (chosen cfg or None, widen us, best us, best cfg)} and
+        the same under (M, N, K, kind) for the mid-M kernel."""
+        from . import silu_mul
+        if not self.enabled:
+            return {}
+        by_shape: dict[tuple[int, int], list[torch.Tensor]] = {}
+        for w in weights:
+            if w.is_cuda and w.dim() == 2 and self.is_weight(w):
+                by_shape.setdefault(self.nk(w), []).append(w)
+        res = {}
+        ms = list(ms)
+        for (N, K), ws in sorted(by_shape.items()):
+            if self.dgemm_mode != "0":
+                kind = ("silu" if (N, K) in silu_shapes else
+                        "tail" if (N, K) in tail_shapes else "plain")
+                self._tune_dgemm(ws, N, K, [m for m in ms if SKINNY_MAX_M < m <= DG_MAX_M],
+                                 dtype, reps, res, kind)
+            sc = [self.scale(w) for w in ws]
+            n = len(ws)
+            for M in sorted(set(m for m in ms if 1 <= m <= SKINNY_MAX_M)):
+                x = torch.randn(M, K, dtype=dtype, device=ws[0].device)
+                out = torch.empty(M, N, dtype=x.dtype, device=x.device)
+
+                def wide():
+                    for w, s in zip(ws, sc):
+                        self.widen_linear(x, w, s)
+                wide_t = _time_graphed(wide, reps)
+                best_t, best = float("inf"), None
+                for cfg in self.configs:
+                    if not self.ok(M, N, K, cfg) or (cfg[0] > 1 and M <= 16 * (cfg[0] // 2)):
+                        continue
+
+                    def fn(cfg=cfg):
+                        for w, s in zip(ws, sc):
+                            self.gemm(x, w, s, None, cfg, out)
+                    t = _time_graphed(fn, reps)
+                    if t < best_t:
+                        best_t, best = t, cfg
+                chosen = best if best_t < wide_t else None
+                self.plan[(M, N, K)] = chosen
+                res[(M, N, K)] = (chosen, wide_t * 1e3 / n, best_t * 1e3 / n, best)
+                log.info("gemm %s M=%d N=%d K=%d: widen + hipBLASLt %.1f us, %s %s %.1f us -> %s",
+                         self.tag, M, N, K, wide_t * 1e3 / n, self.sk, best, best_t * 1e3 / n,
+                         self.sk if chosen else "widen")
+                if (N, K) not in silu_shapes or N % 32:
+                    continue
+                act = torch.empty(M, N // 2, dtype=x.dtype, device=x.device)
+
+                def sep():
+                    for w in ws:
+                        silu_mul(self.linear(x, w), act)
+                sep_t = _time_graphed(sep, reps)
+                sbest_t, sbest = float("inf"), None
+                for cfg in self.configs:
+                    if (cfg[1] != 2 or not self.ok(M, N, K, cfg)
+                            or (cfg[0] > 1 and M <= 16 * (cfg[0] // 2))):
+                        continue
+
+                    def fn(cfg=cfg):
+                        for w, s in zip(ws, sc):
+                            self.silu(x, w, s, cfg, act)
+                    t = _time_graphed(fn, reps)
+                    if t < sbest_t:
+                        sbest_t, sbest = t, cfg
+                self.plan_silu[(M, N, K)] = sbest if sbest_t < sep_t else None
+                log.info("gemm %s M=%d N=%d K=%d silu: plan + silu_mul %.1f us, %s SiLU %s "
+                         "%.1f us", self.tag, M, N, K, sep_t * 1e3 / n, self.sk, sbest,
+                         sbest_t * 1e3 / n)
+        return res
+
+
+# ------------------------------------------------------------------ the two methods
 # K9q configurations: K9's, except (4, 2, 16), which does not fit 128 VGPRs per lane
 _W8_CONFIGS = [c for c in _CONFIGS if c[:3] != (4, 2, 16)]
+# K9f configurations (mt, nt, nw); (4, 2, 8) is not built (64 KB of LDS partial sums)
+_W4_CONFIGS = [(mt, nt, nw) for mt in (1, 2, 4) for nt in (1, 2) for nw in (2, 4, 8)
+               if (mt, nt, nw) != (4, 2, 8)]
 
 
 def w8_ok(M: int, N: int, K: int, cfg) -> bool:
@@ -140,151 +492,6 @@ def w8_default_cfg(M: int, N: int, K: int, silu: bool = False):
     smallest batch tile that holds M, 4 waves, non-temporal loads; None if it does not fit."""
     cfg = (1 if M <= 16 else (2 if M <= 32 else 4), 2 if silu else 1, 4, True)
     return cfg if w8_ok(M, N, K, cfg) and (not silu or N % 32 == 0) else None
-
-
-def w8_gemm(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor,
-            bias: Optional[torch.Tensor], cfg, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """K9q: (x W8^T) * scale (+ bias) in x's dtype."""
-    from . import _k
-    if out is None:
-        out = torch.empty(x.shape[0], w8.shape[0], dtype=x.dtype, device=x.device)
-    _k().w8_gemm(out, x, w8, scale, bias, *cfg, False)
-    _w8_counts["k9q"] += 1
-    return out
-
-
-def w8_silu(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor, cfg,
-            out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """K9q's SiLU form over a merged [gate; up] fp8 weight [2I, K]: out [M, I]."""
-    from . import _k
-    if out is None:
-        out = torch.empty(x.shape[0], w8.shape[0] // 2, dtype=x.dtype, device=x.device)
-    _k().w8_gemm(out, x, w8, scale, None, *cfg, True)
-    _w8_counts["k9q_silu"] += 1
-    return out
-
-
-def w8_reserve(device: torch.device, numel: int, dtype: torch.dtype) -> torch.Tensor:
-    """The widen path's scratch on ``device``: at least ``numel`` elements of ``dtype``.
-    The engine reserves the largest quantised weight before graphs are captured."""
-    key = (device, dtype)
-    s = _w8_scratch.get(key)
-    if s is None or s.numel() < numel:
-        if s is not None:
-            _w8_scratch_old.append(s)
-        s = _w8_scratch[key] = torch.empty(numel, dtype=dtype, device=device)
-    return s
-
-
-def w8_widen(w8: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    """round(w8 * scale) as a [N, K] view of the device's scratch (valid until the next call)."""
-    from . import _k
-    N, K = w8.shape
-    out = w8_reserve(w8.device, N * K, dtype)[: N * K].view(N, K)
-    _k().w8_widen(out, w8, scale)
-    return out
-
-
-def w8_widen_linear(x: torch.Tensor, w8: torch.Tensor, scale: torch.Tensor,
-                    bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    _w8_counts["widen"] += 1
-    return F.linear(x, w8_widen(w8, scale, x.dtype), bias)
-
-
-def _w8_x_ok(x: torch.Tensor) -> bool:
-    return (x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 8 == 0
-            and x.data_ptr() % 16 == 0 and x.dtype in (torch.bfloat16, torch.float16))
-
-
-def w8_linear(x: torch.Tensor, w8: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """A quantised linear layer.  CPU (the oracle, and what the CPU suite runs):
-    x @ (w8.float() * scale[:, None]).T in the activation dtype."""
-    from .quant import dequantize_fp8_rows, w8_scale
-    scale = w8_scale(w8)
-    if not x.is_cuda:
-        return F.linear(x, dequantize_fp8_rows(w8, scale, x.dtype), bias)
-    if x.dim() != 2:
-        return w8_linear(x.reshape(-1, x.shape[-1]), w8, bias).view(*x.shape[:-1], w8.shape[0])
-    M, (N, K) = x.shape[0], w8.shape
-    if _w8_enabled and 1 <= M <= SKINNY_MAX_M and _w8_x_ok(x):
-        key = (M, N, K)
-        cfg = _plan_w8[key] if key in _plan_w8 else w8_default_cfg(M, N, K)
-        if cfg is not None:
-            return w8_gemm(x, w8, scale, bias, cfg)
-    p = _w8_dg_plan(x, w8, "plain")
-    if p is not None and (p[1] == 1 or bias is None):
-        cfg, S = p
-        if S == 1:
-            return w8_dgemm(x, w8, cfg, 1, bias=bias)
-        from . import _k
-        out = torch.empty(M, N, dtype=x.dtype, device=x.device)
-        _k().splitk_reduce(out, w8_dgemm(x, w8, cfg, S))
-        return out
-    return w8_widen_linear(x, w8, scale, bias)
-
-
-def w8_linear_silu(x: torch.Tensor, w8: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    from . import silu_mul
-    from .quant import w8_scale
-    if (_w8_enabled and bias is None and x.is_cuda and _w8_x_ok(x)
-            and 1 <= x.shape[0] <= SKINNY_MAX_M):
-        key = (x.shape[0], w8.shape[0], w8.shape[1])
-        cfg = _plan_w8_silu[key] if key in _plan_w8_silu else w8_default_cfg(*key, silu=True)
-        if cfg is not None:
-            return w8_silu(x, w8, w8_scale(w8), cfg)
-    p = _w8_dg_plan(x, w8, "silu") if bias is None and x.is_cuda else None
-    if p is not None:
-        cfg, S = p
-        if S == 1:
-            return w8_dgemm(x, w8, cfg, 1, epi=2)
-        from . import _k
-        out = torch.empty(x.shape[0], w8.shape[0] // 2, dtype=x.dtype, device=x.device)
-        _k().splitk_reduce_silu(out, w8_dgemm(x, w8, cfg, S, silu_w=True), True)
-        return out
-    return silu_mul(w8_linear(x, w8, bias))
-
-
-def w8_plan() -> dict:
-    return dict(_plan_w8)
-
-
-def w8_silu_plan() -> dict:
-    return dict(_plan_w8_silu)
-
-
-def w8_counts() -> dict:
-    """Calls of each quantised path so far (a captured graph counts once, at capture)."""
-    return dict(_w8_counts)
-
-
-# ------------------------------------------------------------------ W4A16 (--quantization mxfp4)
-# An mxfp4 weight (ops/quant.py) is uint8 codes [N, K/2] carrying its e8m0 block scales
-# [N, K/32]: K is 2 * shape[1] here and nowhere else.  Like fp8 weights it never meets the
-# bf16 plans: every entry point checks the weight's dtype first.
-#   M <= 64: K9f (csrc/kernels/gemm_w4.hip), or -- where start-up timing measured it faster,
-#            or no K9f configuration fits the shape -- the widen path;
-#   M  > 64, prefill: the widen path: kgc.w4_widen writes the exact dequantised weight into
-#            the static scratch fp8 uses (one per device and dtype) and the library GEMM
-#            runs on it.  It moves more bytes than a bf16 weight would -- except at the
-#            decode buckets with 64 < M <= 512 where the plan below names a K9mf
-#            configuration (csrc/kernels/gemm_w4_decode.hip: the K9m pipeline streaming
-#            packed mxfp4 tiles, 0.53 bytes per weight element).
-# (M, N, K) -> K9f cfg (mt, nt, nw), or None where the widen path measured faster
-_plan_w4: dict[tuple[int, int, int], Optional[tuple]] = {}
-# merged gate_up (M, 2I, K) -> cfg of K9f's SiLU form, where it beat the plan + silu_mul
-_plan_w4_silu: dict[tuple[int, int, int], Optional[tuple]] = {}
-_w4_counts = {"k9f": 0, "k9f_silu": 0, "widen": 0, "k9mf": 0, "k9mf_silu": 0}
-_w4_enabled = os.environ.get("KGC_W4_GEMM", "1") != "0"
-# K9mf: (M, N, K, kind) -> (cfg, S), or None where the widen path (with the same consumer)
-# measured faster; kind as in _plan_dg ("plain" | "silu" | "tail").  No entry: widen.
-_plan_w4_dg: dict[tuple[int, int, int, str], Optional[tuple[int, int]]] = {}
-# KGC_W4_DGEMM: "1" tuned (default), "0" off (nothing packed, the widen path runs), "force"
-# (no timing: the first configuration in table order that fits, S = 1 -- tests, A/B runs)
-w4_dgemm_mode = os.environ.get("KGC_W4_DGEMM", "1")
-_U8 = torch.uint8
-# K9f configurations (mt, nt, nw); (4, 2, 8) is not built (64 KB of LDS partial sums)
-_W4_CONFIGS = [(mt, nt, nw) for mt in (1, 2, 4) for nt in (1, 2) for nw in (2, 4, 8)
-               if (mt, nt, nw) != (4, 2, 8)]
 
 
 def w4_ok(M: int, N: int, K: int, cfg) -> bool:
@@ -308,325 +515,60 @@ def w4_default_cfg(M: int, N: int, K: int, silu: bool = False):
     return None
 
 
-def w4_gemm(x: torch.Tensor, w4: torch.Tensor, scales: torch.Tensor,
-            bias: Optional[torch.Tensor], cfg, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """K9f: x dq(W4)^T (+ bias) in x's dtype."""
-    from . import _k
-    if out is None:
-        out = torch.empty(x.shape[0], w4.shape[0], dtype=x.dtype, device=x.device)
-    _k().w4_gemm(out, x, w4, scales, bias, *cfg, False)
-    _w4_counts["k9f"] += 1
-    return out
+def _w8_op_mid(out, x, w8, e, bias, cfg, epi) -> None:
+    # the SiLU-packed tiles' columns are gate / up groups interleaved, so their split-K
+    # slices (epi 0) take the scales in tile row order: the entry's extra
+    sc = e[2] if epi == 0 and e[2] is not None else w8_scale(w8)
+    _kgc().w8_dgemm(out, x, e[1], sc, bias, cfg, epi)
 
 
-def w4_silu(x: torch.Tensor, w4: torch.Tensor, scales: torch.Tensor, cfg,
-            out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """K9f's SiLU form over a merged [gate; up] mxfp4 weight [2I, K]: out [M, I]."""
-    from . import _k
-    if out is None:
-        out = torch.empty(x.shape[0], w4.shape[0] // 2, dtype=x.dtype, device=x.device)
-    _k().w4_gemm(out, x, w4, scales, None, *cfg, True)
-    _w4_counts["k9f_silu"] += 1
-    return out
+def _w8_op_pack(p, w8, silu):
+    _kgc().w8_dgemm_pack(p, w8.detach(), silu)
+    # a SiLU slice's column c is weight row tile_rows[c]
+    return w8_scale(w8)[tile_rows(w8.shape[0], True, w8.device).flatten()].contiguous() \
+        if silu else None
 
 
-def w4_widen(w4: torch.Tensor, scales: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
-    """The exact dequantised weight as a [N, K] view of the device's scratch (the one
-    ``w8_reserve`` keeps; valid until the next widen of either method)."""
-    from . import _k
-    N, K = w4.shape[0], 2 * w4.shape[1]
-    out = w8_reserve(w4.device, N * K, dtype)[: N * K].view(N, K)
-    _k().w4_widen(out, w4, scales)
-    return out
+def _w4_op_pack(p, w4, silu):
+    _kgc().w4_dgemm_pack(p, w4.detach(), w4_scale(w4), silu)
 
 
-def w4_widen_linear(x: torch.Tensor, w4: torch.Tensor, scales: torch.Tensor,
-                    bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    _w4_counts["widen"] += 1
-    return F.linear(x, w4_widen(w4, scales, x.dtype), bias)
+W8 = QuantMethod(
+    method="fp8", tag="W8", sk="K9q", mid="K9mq", configs=_W8_CONFIGS, ok=w8_ok,
+    default_cfg=w8_default_cfg, is_weight=is_fp8, nk=lambda w: (w.shape[0], w.shape[1]),
+    scale=w8_scale, dequant=dequantize_fp8_rows, tile_bytes=8192,
+    op_gemm=lambda *a: _kgc().w8_gemm(*a), op_widen=lambda *a: _kgc().w8_widen(*a),
+    op_mid=_w8_op_mid, op_pack=_w8_op_pack,
+    op_tiles=lambda: [_kgc().w8_dgemm_cfg_info(c) for c in range(int(_kgc().w8_dgemm_num_cfgs()))])
+W4 = QuantMethod(
+    method="mxfp4", tag="W4", sk="K9f", mid="K9mf", configs=_W4_CONFIGS, ok=w4_ok,
+    default_cfg=w4_default_cfg, is_weight=is_mxfp4, nk=lambda w: (w.shape[0], 2 * w.shape[1]),
+    scale=w4_scale, dequant=dequantize_mxfp4, tile_bytes=MXFP4_TILE_BYTES,
+    op_gemm=lambda *a: _kgc().w4_gemm(*a), op_widen=lambda *a: _kgc().w4_widen(*a),
+    op_mid=lambda out, x, w4, e, bias, cfg, epi: _kgc().w4_dgemm(out, x, e[1], bias, cfg, epi),
+    op_pack=_w4_op_pack,
+    op_tiles=lambda: [_kgc().w4_dgemm_cfg_info(c) for c in range(int(_kgc().w4_dgemm_num_cfgs()))])
+QUANT_METHODS = {q.method: q for q in (W8, W4)}
+
+# the names callers use, bound to the shared implementation; the plan dicts are the
+# instances' own objects (tests write into them, ``clear_plan`` clears them in place)
+_plan_w8, _plan_w8_silu, _plan_w8_dg = W8.plan, W8.plan_silu, W8.plan_dg
+_plan_w4, _plan_w4_silu, _plan_w4_dg = W4.plan, W4.plan_silu, W4.plan_dg
+w8_gemm, w8_silu, w8_widen, w8_widen_linear = W8.gemm, W8.silu, W8.widen, W8.widen_linear
+w4_gemm, w4_silu, w4_widen, w4_widen_linear = W4.gemm, W4.silu, W4.widen, W4.widen_linear
+w8_linear, w8_linear_silu, w8_dgemm, tune_w8 = W8.linear, W8.linear_silu, W8.dgemm, W8.tune
+w4_linear, w4_linear_silu, w4_dgemm, tune_w4 = W4.linear, W4.linear_silu, W4.dgemm, W4.tune
+pack_w8_decode_weights, _w8_dg_tiles = W8.pack_decode_weights, W8.tiles
+pack_w4_decode_weights, _w4_dg_tiles = W4.pack_decode_weights, W4.tiles
+w8_plan, w8_silu_plan = partial(dict, W8.plan), partial(dict, W8.plan_silu)
+w4_plan, w4_silu_plan = partial(dict, W4.plan), partial(dict, W4.plan_silu)
+w8_dg_plan, w4_dg_plan = partial(dict, W8.plan_dg), partial(dict, W4.plan_dg)
+# calls of each quantised path so far (a captured graph counts once, at capture)
+w8_counts, w4_counts = partial(dict, W8.counts), partial(dict, W4.counts)
+w8_dg_ok = w4_dg_ok = q_dg_ok
 
 
-def w4_linear(x: torch.Tensor, w4: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """An mxfp4 linear layer.  CPU (the oracle, and what the CPU suite runs): F.linear on
-    the dequantised weight in the activation dtype."""
-    from .quant import dequantize_mxfp4, w4_scale
-    scales = w4_scale(w4)
-    if not x.is_cuda:
-        return F.linear(x, dequantize_mxfp4(w4, scales, x.dtype), bias)
-    N, K = w4.shape[0], 2 * w4.shape[1]
-    if x.dim() != 2:
-        return w4_linear(x.reshape(-1, x.shape[-1]), w4, bias).view(*x.shape[:-1], N)
-    M = x.shape[0]
-    if _w4_enabled and 1 <= M <= SKINNY_MAX_M and _w8_x_ok(x):
-        key = (M, N, K)
-        cfg = _plan_w4[key] if key in _plan_w4 else w4_default_cfg(M, N, K)
-        if cfg is not None:
-            return w4_gemm(x, w4, scales, bias, cfg)
-    p = _w4_dg_plan(x, w4, "plain")
-    if p is not None and (p[1] == 1 or bias is None):
-        cfg, S = p
-        if S == 1:
-            return w4_dgemm(x, w4, cfg, 1, bias=bias)
-        from . import _k
-        out = torch.empty(M, N, dtype=x.dtype, device=x.device)
-        _k().splitk_reduce(out, w4_dgemm(x, w4, cfg, S))
-        return out
-    return w4_widen_linear(x, w4, scales, bias)
-
-
-def w4_linear_silu(x: torch.Tensor, w4: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
-    from . import silu_mul
-    from .quant import w4_scale
-    if (_w4_enabled and bias is None and x.is_cuda and _w8_x_ok(x)
-            and 1 <= x.shape[0] <= SKINNY_MAX_M):
-        key = (x.shape[0], w4.shape[0], 2 * w4.shape[1])
-        cfg = _plan_w4_silu[key] if key in _plan_w4_silu else w4_default_cfg(*key, silu=True)
-        if cfg is not None:
-            return w4_silu(x, w4, w4_scale(w4), cfg)
-    p = _w4_dg_plan(x, w4, "silu") if bias is None and x.is_cuda else None
-    if p is not None:
-        cfg, S = p
-        if S == 1:
-            return w4_dgemm(x, w4, cfg, 1, epi=2)
-        from . import _k
-        out = torch.empty(x.shape[0], w4.shape[0] // 2, dtype=x.dtype, device=x.device)
-        _k().splitk_reduce_silu(out, w4_dgemm(x, w4, cfg, S, silu_w=True), True)
-        return out
-    return silu_mul(w4_linear(x, w4, bias))
-
-
-def w4_plan() -> dict:
-    return dict(_plan_w4)
-
-
-def w4_silu_plan() -> dict:
-    return dict(_plan_w4_silu)
-
-
-def w4_counts() -> dict:
-    """Calls of each mxfp4 path so far (a captured graph counts once, at capture)."""
-    return dict(_w4_counts)
-
-
-@torch.inference_mode()
-def tune_w4(weights: Iterable[torch.Tensor], ms: Iterable[int], dtype: torch.dtype,
-            silu_shapes=(), reps: int = 3, tail_shapes=()) -> dict:
-    """For each mxfp4 weight shape and decode bucket M <= 64: every K9f configuration against
-    the widen path, graph-replayed over ALL weights of the shape (HBM-resident, as in a
-    decode step); the faster goes into the W4 plan.  ``silu_shapes``: (N, K) of merged
-    gate_up weights, whose SiLU form is timed against the plain winner + silu_mul.
-    Decode buckets with 64 < M <= 512: the K9mf candidates against the widen path, each
-    with its consumer (``_tune_w4_dgemm``; ``tail_shapes``: (N, K) of the o / down
-    projections that feed ``linear_add_rms``), only for the weights
-    ``pack_w4_decode_weights`` packed -- the results go into ``w4_dg_plan()``, never into
-    ``w4_plan()``.  Returns {(M, N, K): (chosen cfg or None, widen us, best K9f us, best K9f
-    cfg)} and the same under (M, N, K, kind) for K9mf."""
-    from . import silu_mul
-    from .quant import is_mxfp4, w4_scale
-    if not _w4_enabled:
-        return {}
-    by_shape: dict[tuple[int, int], list[torch.Tensor]] = {}
-    for w in weights:
-        if w.is_cuda and w.dim() == 2 and is_mxfp4(w):
-            by_shape.setdefault((w.shape[0], 2 * w.shape[1]), []).append(w)
-    res = {}
-    ms = list(ms)
-    for (N, K), ws in sorted(by_shape.items()):
-        if w4_dgemm_mode != "0":
-            kind = ("silu" if (N, K) in silu_shapes else
-                    "tail" if (N, K) in tail_shapes else "plain")
-            _tune_w4_dgemm(ws, N, K, [m for m in ms if SKINNY_MAX_M < m <= DG_MAX_M], dtype,
-                           reps, res, kind)
-        sc = [w4_scale(w) for w in ws]
-        n = len(ws)
-        for M in sorted(set(m for m in ms if 1 <= m <= SKINNY_MAX_M)):
-            x = torch.randn(M, K, dtype=dtype, device=ws[0].device)
-            out = torch.empty(M, N, dtype=x.dtype, device=x.device)
-
-            def wide():
-                for w, s in zip(ws, sc):
-                    w4_widen_linear(x, w, s)
-            wide_t = _time_graphed(wide, reps)
-            best_t, best = float("inf"), None
-            for cfg in _W4_CONFIGS:
-                if not w4_ok(M, N, K, cfg) or (cfg[0] > 1 and M <= 16 * (cfg[0] // 2)):
-                    continue
-
-                def fn(cfg=cfg):
-                    for w, s in zip(ws, sc):
-                        w4_gemm(x, w, s, None, cfg, out)
-                t = _time_graphed(fn, reps)
-                if t < best_t:
-                    best_t, best = t, cfg
-            chosen = best if best_t < wide_t else None
-            _plan_w4[(M, N, K)] = chosen
-            res[(M, N, K)] = (chosen, wide_t * 1e3 / n, best_t * 1e3 / n, best)
-            log.info("gemm W4 M=%d N=%d K=%d: widen + hipBLASLt %.1f us, K9f %s %.1f us -> %s",
-                     M, N, K, wide_t * 1e3 / n, best, best_t * 1e3 / n,
-                     "K9f" if chosen else "widen")
-            if (N, K) not in silu_shapes or N % 32:
-                continue
-            act = torch.empty(M, N // 2, dtype=x.dtype, device=x.device)
-
-            def sep():
-                for w in ws:
-                    silu_mul(w4_linear(x, w), act)
-            sep_t = _time_graphed(sep, reps)
-            sbest_t, sbest = float("inf"), None
-            for cfg in _W4_CONFIGS:
-                if (cfg[1] != 2 or not w4_ok(M, N, K, cfg)
-                        or (cfg[0] > 1 and M <= 16 * (cfg[0] // 2))):
-                    continue
-
-                def fn(cfg=cfg):
-                    for w, s in zip(ws, sc):
-                        w4_silu(x, w, s, cfg, act)
-                t = _time_graphed(fn, reps)
-                if t < sbest_t:
-                    sbest_t, sbest = t, cfg
-            _plan_w4_silu[(M, N, K)] = sbest if sbest_t < sep_t else None
-            log.info("gemm W4 M=%d N=%d K=%d silu: plan + silu_mul %.1f us, K9f SiLU %s %.1f us",
-                     M, N, K, sep_t * 1e3 / n, sbest, sbest_t * 1e3 / n)
-    return res
-
-
-# ------------------------------------------------------------------ K9mq (64 < M <= 512)
-_W8_DG_TILES: list = []          # (BM, BN, ring slots) per configuration id, read once
-
-
-def _w8_dg_tiles() -> list:
-    if not _W8_DG_TILES:
-        from . import _k
-        _W8_DG_TILES.extend(tuple(int(v) for v in _k().w8_dgemm_cfg_info(c))
-                            for c in range(int(_k().w8_dgemm_num_cfgs())))
-    return _W8_DG_TILES
-
-
-def w8_dg_ok(M: int, N: int, K: int, cfg: int = 0, S: int = 1) -> bool:
-    """Shapes K9mq takes: 64 < M <= 512, N in whole 128-column tiles, K in whole 64-k steps,
-    at most one K-slice per step (and the 32 slices the binding allows)."""
-    return (SKINNY_MAX_M < M <= DG_MAX_M and N >= 128 and N % 128 == 0 and K >= 64
-            and K % 64 == 0 and cfg >= 0 and 1 <= S <= min(32, K // 64))
-
-
-def w8_dg_plan() -> dict:
-    return dict(_plan_w8_dg)
-
-
-def _q_packed_entry(w: torch.Tensor, silu: bool) -> Optional[tuple]:
-    """The registry entry (weakref, packed tiles, extra) of a quantised weight's packed copy
-    (K9mq's e4m3 tiles or K9mf's mxfp4 tiles), or None."""
-    key = (w.data_ptr(), silu)
-    e = _q_packed.get(key)
-    if e is None:
-        return None
-    src = e[0]()
-    if src is None:
-        _q_packed.pop(key, None)
-        return None
-    if src.data_ptr() != w.data_ptr() or src.shape != w.shape or src.dtype != w.dtype:
-        return None
-    return e
-
-
-def _q_packed_get(w: torch.Tensor, silu: bool) -> Optional[torch.Tensor]:
-    e = _q_packed_entry(w, silu)
-    return None if e is None else e[1]
-
-
-def _q_packed_put(w: torch.Tensor, silu: bool, p: torch.Tensor, extra=None) -> None:
-    key = (w.data_ptr(), silu)
-
-    def drop(ref, key=key):
-        e = _q_packed.get(key)
-        if e is not None and e[0] is ref:
-            del _q_packed[key]
-    _q_packed[key] = (weakref.ref(w, drop), p, extra)
-
-
-def _w8_packed_put(w8: torch.Tensor, silu: bool, p: torch.Tensor) -> None:
-    from .quant import tile_rows, w8_scale
-    # the SiLU-packed tiles' columns are gate / up groups interleaved: a slice's column c
-    # is weight row tile_rows[c], so the slices take the scales in that order
-    sc = w8_scale(w8)[tile_rows(w8.shape[0], True, w8.device).flatten()].contiguous() if silu \
-        else None
-    _q_packed_put(w8, silu, p, sc)
-
-
-def w8_packed_weight(w8: torch.Tensor, silu: bool = False) -> Optional[torch.Tensor]:
-    return _q_packed_get(w8, silu)
-
-
-def pack_w8_decode_weights(plain: Iterable[torch.Tensor], silu: Iterable[torch.Tensor]) -> int:
-    """Packed e4m3 copies ([N/128][K/64][128 rows x 64 B] tiles, ``quant.pack_fp8_tiles_reference``)
-    of a quantised model's decode-GEMM weights for K9mq, made once before the KV cache is
-    sized.  ``silu``: merged gate_up weights, packed with gate and up 16-row groups
-    interleaved.  Nothing is packed (the widen path stays) with KGC_W8_DGEMM=0 or when the
-    copies would exceed KGC_DGEMM_PACK_FRACTION of device memory.  Returns bytes packed."""
-    if w8_dgemm_mode == "0" or not _w8_enabled:
-        return 0
-    from . import _k
-    todo = []
-    for w, sl in [(w, False) for w in plain] + [(w, True) for w in silu]:
-        if (w.is_cuda and w.dim() == 2 and w.dtype == _FP8 and w.is_contiguous()
-                and w.shape[0] % 128 == 0 and w.shape[1] % 64 == 0
-                and (not sl or (w.shape[0] // 2) % 64 == 0) and _q_packed_get(w, sl) is None):
-            todo.append((w, sl))
-    need = sum(w.numel() for w, _ in todo)
-    if not todo:
-        return 0
-    free, total = torch.cuda.mem_get_info(todo[0][0].device)
-    if need > _PACK_FRACTION * total or need > free - (8 << 30):
-        log.info("K9mq: %.1f GB of packed fp8 weights exceeds the budget; widen path only",
-                 need / 1e9)
-        return 0
-    for w, sl in todo:
-        N, K = w.shape
-        p = torch.empty(N // 128, K // 64, 8192, dtype=w.dtype, device=w.device)
-        _k().w8_dgemm_pack(p, w.detach(), sl)
-        _w8_packed_put(w, sl, p)
-    log.info("K9mq: packed %d fp8 decode weights (%.2f GB, out of the KV pool; "
-             "KGC_W8_DGEMM=0 returns them)", len(todo), need / 1e9)
-    return need
-
-
-def w8_dgemm(x: torch.Tensor, w8: torch.Tensor, cfg: int, S: int, epi: int = 1,
-             out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
-             silu_w: bool = False) -> torch.Tensor:
-    """K9mq over ``w8``'s packed copy: S == 1 -> (x W8^T) * scale (+ bias) in x's dtype
-    (epi 1) or the SiLU pairs [M, N/2] of a merged gate_up weight (epi 2); S > 1 -> the
-    [S, M, N] fp32 K-slices, each already scaled (the caller's consumer sums them).
-    silu_w: slices of the SiLU-packed copy (``splitk_reduce_silu(interleaved=True)``)."""
-    from . import _k
-    from .quant import w8_scale
-    silu = epi == 2 or silu_w
-    e = _q_packed_entry(w8, silu)
-    if e is None:
-        raise RuntimeError("K9mq: the weight has no packed copy (pack_w8_decode_weights)")
-    wp = e[1]
-    M, N = x.shape[0], w8.shape[0]
-    if S > 1:
-        if bias is not None:
-            raise RuntimeError("K9mq: no bias on split-K slices")
-        out = torch.empty(S, M, N, dtype=torch.float32, device=x.device) if out is None else out
-        _k().w8_dgemm(out, x, wp, e[2] if silu else w8_scale(w8), None, cfg, 0)
-    else:
-        if out is None:
-            out = torch.empty(M, N // 2 if epi == 2 else N, dtype=x.dtype, device=x.device)
-        _k().w8_dgemm(out, x, wp, w8_scale(w8), bias, cfg, epi)
-    _w8_counts["k9mq_silu" if silu else "k9mq"] += 1
-    return out
-
-
-def _w8_dg_plan(x: torch.Tensor, w8: torch.Tensor, kind: str):
-    """The K9mq (cfg, S) of this call, or None: no entry, a None entry, the knob off, an X
-    the kernel does not take, or a weight without its packed copy -> the widen path."""
-    if not _plan_w8_dg or w8_dgemm_mode == "0" or not x.is_cuda or not _w8_x_ok(x):
-        return None
-    p = _plan_w8_dg.get((x.shape[0], w8.shape[0], w8.shape[1], kind))
-    if p is None or _q_packed_get(w8, kind == "silu") is None:
-        return None
-    return p
+w8_packed_weight = w4_packed_weight = _packed_get
 
 
 def _q_dg_candidates(M: int, N: int, K: int, tiles: list):
@@ -639,7 +581,7 @@ def _q_dg_candidates(M: int, N: int, K: int, tiles: list):
             continue
         wgs = ((M + bm - 1) // bm) * (N // bn)
         for S in _DG_SPLITS:
-            if not w8_dg_ok(M, N, K, c, S) or (S > 1 and wgs * S > _DG_MAX_GRID):
+            if not q_dg_ok(M, N, K, c, S) or (S > 1 and wgs * S > _DG_MAX_GRID):
                 continue
             out.append((c, S))
     return out
@@ -658,11 +600,11 @@ def _tune_q_dgemm(n: int, dev, N: int, K: int, ms, dtype, reps: int, res: dict, 
     from . import _k, fused_add_rms_norm, silu_mul
     silu = kind == "silu"
     for M in sorted(set(ms)):
-        if not w8_dg_ok(M, N, K) or (kind == "tail" and N > 8192):
+        if not q_dg_ok(M, N, K) or (kind == "tail" and N > 8192):
             continue
         key = (M, N, K, kind)
         if mode == "force":
-            first = next((c for c in range(len(tiles)) if w8_dg_ok(M, N, K, c, 1)), None)
+            first = next((c for c in range(len(tiles)) if q_dg_ok(M, N, K, c, 1)), None)
             if first is not None:
                 plan[key] = (first, 1)
                 res[key] = ((first, 1), float("nan"), float("nan"), (first, 1))
@@ -725,220 +667,6 @@ def _tune_q_dgemm(n: int, dev, N: int, K: int, ms, dtype, reps: int, res: dict, 
                  tag, M, N, K, kind, wide_t * 1e3 / n, kname, best, best_t * 1e3 / n,
                  kname if chosen else "widen")
 
-
-def _tune_w8_dgemm(ws, N: int, K: int, ms, dtype, reps: int, res: dict, kind: str) -> None:
-    """``_tune_q_dgemm`` for K9mq over the fp8 weights ``ws`` of one shape (all packed, or
-    nothing is tuned).  KGC_W8_DGEMM=force: no timing."""
-    from . import _k
-    from .quant import w8_scale
-    silu = kind == "silu"
-    if any(_q_packed_get(w, silu) is None for w in ws):
-        return
-    sc = [w8_scale(w) for w in ws]
-    wps = [_q_packed_get(w, silu) for w in ws]
-    sc_il = [_q_packed_entry(w, silu)[2] for w in ws]      # silu slices: tile row order
-
-    def launch(buf, x, i, cfg, epi):
-        _k().w8_dgemm(buf, x, wps[i], (sc_il if silu and epi == 0 else sc)[i], None, cfg, epi)
-    _tune_q_dgemm(len(ws), ws[0].device, N, K, ms, dtype, reps, res, kind, tag="W8",
-                  kname="K9mq", mode=w8_dgemm_mode, plan=_plan_w8_dg, tiles=_w8_dg_tiles(),
-                  wide_linear=lambda x, i: w8_widen_linear(x, ws[i], sc[i]), launch=launch)
-
-
-# ------------------------------------------------------------------ K9mf (64 < M <= 512)
-_W4_DG_TILES: list = []          # (BM, BN, ring slots) per configuration id, read once
-
-
-def _w4_dg_tiles() -> list:
-    if not _W4_DG_TILES:
-        from . import _k
-        _W4_DG_TILES.extend(tuple(int(v) for v in _k().w4_dgemm_cfg_info(c))
-                            for c in range(int(_k().w4_dgemm_num_cfgs())))
-    return _W4_DG_TILES
-
-
-def w4_dg_ok(M: int, N: int, K: int, cfg: int = 0, S: int = 1) -> bool:
-    """Shapes K9mf takes (K the layer's, not the code bytes): K9mq's -- 64 < M <= 512, N in
-    whole 128-column tiles, K in whole 64-k steps, at most one K-slice per step (and the 32
-    slices the binding allows)."""
-    return w8_dg_ok(M, N, K, cfg, S)
-
-
-def w4_dg_plan() -> dict:
-    return dict(_plan_w4_dg)
-
-
-def w4_packed_weight(w4: torch.Tensor, silu: bool = False) -> Optional[torch.Tensor]:
-    return _q_packed_get(w4, silu)
-
-
-def pack_w4_decode_weights(plain: Iterable[torch.Tensor], silu: Iterable[torch.Tensor]) -> int:
-    """Packed copies ([N/128][K/64][4096 B codes + 256 B scales] tiles,
-    ``quant.pack_mxfp4_tiles_reference``) of an mxfp4 model's decode-GEMM weights for K9mf,
-    made once before the KV cache is sized.  ``silu``: merged gate_up weights, packed with
-    gate and up 16-row groups interleaved.  Nothing is packed (the widen path stays) with
-    KGC_W4_DGEMM=0 or when the copies would exceed KGC_DGEMM_PACK_FRACTION of device memory.
-    Returns bytes packed."""
-    if w4_dgemm_mode == "0" or not _w4_enabled:
-        return 0
-    from . import _k
-    from .quant import MXFP4_TILE_BYTES, is_mxfp4, w4_scale
-    todo = []
-    for w, sl in [(w, False) for w in plain] + [(w, True) for w in silu]:
-        if (w.is_cuda and w.dim() == 2 and is_mxfp4(w) and w.is_contiguous()
-                and w.shape[0] % 128 == 0 and w.shape[1] % 32 == 0
-                and (not sl or (w.shape[0] // 2) % 64 == 0) and _q_packed_get(w, sl) is None):
-            todo.append((w, sl))
-    need = sum(w.shape[0] // 128 * (w.shape[1] // 32) * MXFP4_TILE_BYTES for w, _ in todo)
-    if not todo:
-        return 0
-    free, total = torch.cuda.mem_get_info(todo[0][0].device)
-    if need > _PACK_FRACTION * total or need > free - (8 << 30):
-        log.info("K9mf: %.1f GB of packed mxfp4 weights exceeds the budget; widen path only",
-                 need / 1e9)
-        return 0
-    for w, sl in todo:
-        p = torch.empty(w.shape[0] // 128, w.shape[1] // 32, MXFP4_TILE_BYTES, dtype=_U8,
-                        device=w.device)
-        _k().w4_dgemm_pack(p, w.detach(), w4_scale(w), sl)
-        _q_packed_put(w, sl, p)
-    log.info("K9mf: packed %d mxfp4 decode weights (%.2f GB, out of the KV pool; "
-             "KGC_W4_DGEMM=0 returns them)", len(todo), need / 1e9)
-    return need
-
-
-def w4_dgemm(x: torch.Tensor, w4: torch.Tensor, cfg: int, S: int, epi: int = 1,
-             out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
-             silu_w: bool = False) -> torch.Tensor:
-    """K9mf over ``w4``'s packed copy: S == 1 -> x dq(W4)^T (+ bias) in x's dtype (epi 1) or
-    the SiLU pairs [M, N/2] of a merged gate_up weight (epi 2); S > 1 -> the [S, M, N] fp32
-    K-slices (the caller's consumer sums them).  silu_w: slices of the SiLU-packed copy
-    (``splitk_reduce_silu(interleaved=True)``)."""
-    from . import _k
-    silu = epi == 2 or silu_w
-    wp = _q_packed_get(w4, silu)
-    if wp is None:
-        raise RuntimeError("K9mf: the weight has no packed copy (pack_w4_decode_weights)")
-    M, N = x.shape[0], w4.shape[0]
-    if S > 1:
-        if bias is not None:
-            raise RuntimeError("K9mf: no bias on split-K slices")
-        out = torch.empty(S, M, N, dtype=torch.float32, device=x.device) if out is None else out
-        _k().w4_dgemm(out, x, wp, None, cfg, 0)
-    else:
-        if out is None:
-            out = torch.empty(M, N // 2 if epi == 2 else N, dtype=x.dtype, device=x.device)
-        _k().w4_dgemm(out, x, wp, bias, cfg, epi)
-    _w4_counts["k9mf_silu" if silu else "k9mf"] += 1
-    return out
-
-
-def _w4_dg_plan(x: torch.Tensor, w4: torch.Tensor, kind: str):
-    """The K9mf (cfg, S) of this call, or None: no entry, a None entry, the knob off, an X
-    the kernel does not take, or a weight without its packed copy -> the widen path."""
-    if not _plan_w4_dg or w4_dgemm_mode == "0" or not x.is_cuda or not _w8_x_ok(x):
-        return None
-    p = _plan_w4_dg.get((x.shape[0], w4.shape[0], 2 * w4.shape[1], kind))
-    if p is None or _q_packed_get(w4, kind == "silu") is None:
-        return None
-    return p
-
-
-def _tune_w4_dgemm(ws, N: int, K: int, ms, dtype, reps: int, res: dict, kind: str) -> None:
-    """``_tune_q_dgemm`` for K9mf over the mxfp4 weights ``ws`` of one shape (all packed, or
-    nothing is tuned: the tuner never packs).  KGC_W4_DGEMM=force: no timing."""
-    from . import _k
-    from .quant import w4_scale
-    silu = kind == "silu"
-    if any(_q_packed_get(w, silu) is None for w in ws):
-        return
-    sc = [w4_scale(w) for w in ws]
-    wps = [_q_packed_get(w, silu) for w in ws]
-    _tune_q_dgemm(len(ws), ws[0].device, N, K, ms, dtype, reps, res, kind, tag="W4",
-                  kname="K9mf", mode=w4_dgemm_mode, plan=_plan_w4_dg, tiles=_w4_dg_tiles(),
-                  wide_linear=lambda x, i: w4_widen_linear(x, ws[i], sc[i]),
-                  launch=lambda buf, x, i, cfg, epi: _k().w4_dgemm(buf, x, wps[i], None, cfg, epi))
-
-
-@torch.inference_mode()
-def tune_w8(weights: Iterable[torch.Tensor], ms: Iterable[int], dtype: torch.dtype,
-            silu_shapes=(), reps: int = 3, tail_shapes=()) -> dict:
-    """For each fp8 weight shape and decode bucket M <= 64: every K9q configuration against
-    the widen path, graph-replayed over ALL weights of the shape (HBM-resident, as in a
-    decode step); the faster goes into the W8 plan.  ``silu_shapes``: (N, K) of merged
-    gate_up weights, whose SiLU form is timed against the plain winner + silu_mul.
-    Decode buckets with 64 < M <= 512: the K9mq candidates against the widen path, each
-    with its consumer (``_tune_w8_dgemm``; ``tail_shapes``: (N, K) of the o / down
-    projections that feed ``linear_add_rms``), for the weights ``pack_w8_decode_weights``
-    packed.  Returns {(M, N, K): (chosen cfg or None, widen us, best K9q us, best K9q cfg)}
-    and the same under (M, N, K, kind) for K9mq."""
-    from . import silu_mul
-    from .quant import is_fp8, w8_scale
-    if not _w8_enabled:
-        return {}
-    by_shape: dict[tuple[int, int], list[torch.Tensor]] = {}
-    for w in weights:
-        if w.is_cuda and w.dim() == 2 and is_fp8(w):
-            by_shape.setdefault((w.shape[0], w.shape[1]), []).append(w)
-    res = {}
-    ms = list(ms)
-    for (N, K), ws in sorted(by_shape.items()):
-        if w8_dgemm_mode != "0":
-            kind = ("silu" if (N, K) in silu_shapes else
-                    "tail" if (N, K) in tail_shapes else "plain")
-            _tune_w8_dgemm(ws, N, K, [m for m in ms if SKINNY_MAX_M < m <= DG_MAX_M], dtype,
-                           reps, res, kind)
-        sc = [w8_scale(w) for w in ws]
-        for M in sorted(set(m for m in ms if 1 <= m <= SKINNY_MAX_M)):
-            x = torch.randn(M, K, dtype=dtype, device=ws[0].device)
-            out = torch.empty(M, N, dtype=x.dtype, device=x.device)
-
-            def wide():
-                for w, s in zip(ws, sc):
-                    w8_widen_linear(x, w, s)
-            wide_t = _time_graphed(wide, reps)
-            best_t, best = float("inf"), None
-            for cfg in _W8_CONFIGS:
-                if not w8_ok(M, N, K, cfg) or (cfg[0] > 1 and M <= 16 * (cfg[0] // 2)):
-                    continue
-
-                def fn(cfg=cfg):
-                    for w, s in zip(ws, sc):
-                        w8_gemm(x, w, s, None, cfg, out)
-                t = _time_graphed(fn, reps)
-                if t < best_t:
-                    best_t, best = t, cfg
-            chosen = best if best_t < wide_t else None
-            _plan_w8[(M, N, K)] = chosen
-            n = len(ws)
-            res[(M, N, K)] = (chosen, wide_t * 1e3 / n, best_t * 1e3 / n, best)
-            log.info("gemm W8 M=%d N=%d K=%d: widen + hipBLASLt %.1f us, K9q %s %.1f us -> %s",
-                     M, N, K, wide_t * 1e3 / n, best, best_t * 1e3 / n,
-                     "K9q" if chosen else "widen")
-            if (N, K) not in silu_shapes or N % 32:
-                continue
-            act = torch.empty(M, N // 2, dtype=x.dtype, device=x.device)
-
-            def sep():
-                for w in ws:
-                    silu_mul(w8_linear(x, w), act)
-            sep_t = _time_graphed(sep, reps)
-            sbest_t, sbest = float("inf"), None
-            for cfg in _W8_CONFIGS:
-                if (cfg[1] != 2 or not w8_ok(M, N, K, cfg)
-                        or (cfg[0] > 1 and M <= 16 * (cfg[0] // 2))):
-                    continue
-
-                def fn(cfg=cfg):
-                    for w, s in zip(ws, sc):
-                        w8_silu(x, w, s, cfg, act)
-                t = _time_graphed(fn, reps)
-                if t < sbest_t:
-                    sbest_t, sbest = t, cfg
-            _plan_w8_silu[(M, N, K)] = sbest if sbest_t < sep_t else None
-            log.info("gemm W8 M=%d N=%d K=%d silu: plan + silu_mul %.1f us, K9q SiLU %s %.1f us",
-                     M, N, K, sep_t * 1e3 / n, sbest, sbest_t * 1e3 / n)
-    return res
 
 
 def _dg_info(cfg: int):
@@ -1078,25 +806,9 @@ def linear_add_rms(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor,
     one kernel (``splitk_add_rms_norm``); otherwise the GEMM and ``fused_add_rms_norm``."""
     from . import _k, fused_add_rms_norm
     if w.dtype == _FP8:
-        p = _w8_dg_plan(x, w, "tail") if x.is_cuda else None
-        if p is not None and w.shape[0] <= 8192 and residual.is_contiguous():
-            cfg, S = p
-            if S > 1:
-                out = torch.empty_like(residual)
-                _k().splitk_add_rms_norm(out, w8_dgemm(x, w, cfg, S), residual, gamma, eps)
-                return out, residual
-            return fused_add_rms_norm(w8_dgemm(x, w, cfg, 1), residual, gamma, eps)
-        return fused_add_rms_norm(w8_linear(x, w), residual, gamma, eps)
+        return W8.linear_add_rms(x, w, residual, gamma, eps)
     if w.dtype == _U8:
-        p = _w4_dg_plan(x, w, "tail") if x.is_cuda else None
-        if p is not None and w.shape[0] <= 8192 and residual.is_contiguous():
-            cfg, S = p
-            if S > 1:
-                out = torch.empty_like(residual)
-                _k().splitk_add_rms_norm(out, w4_dgemm(x, w, cfg, S), residual, gamma, eps)
-                return out, residual
-            return fused_add_rms_norm(w4_dgemm(x, w, cfg, 1), residual, gamma, eps)
-        return fused_add_rms_norm(w4_linear(x, w), residual, gamma, eps)
+        return W4.linear_add_rms(x, w, residual, gamma, eps)
     if _plan_accnorm and x.is_cuda and x.dim() == 2 and x.stride(1) == 1:
         cfg = _plan_accnorm.get((x.shape[0], w.shape[0], w.shape[1]))
         if cfg is not None and residual.is_contiguous():
@@ -1383,12 +1095,10 @@ def save_dg_table(path: str, res: dict, meta: dict) -> int:
 
 
 def clear_plan() -> None:
-    _plan_w8_dg.clear()
-    _plan_w4_dg.clear()
-    _plan_w8.clear()
-    _plan_w8_silu.clear()
-    _plan_w4.clear()
-    _plan_w4_silu.clear()
+    for q in (W8, W4):
+        q.plan_dg.clear()
+        q.plan.clear()
+        q.plan_silu.clear()
     _dg_table.clear()
     _best_sk.clear()
     _best_silu.clear()
@@ -1422,9 +1132,7 @@ def tail_plan_has_m(M: int) -> bool:
     """A fused projection-tail plan at this M: K9m split-K (M > 64) or SK_ACC_NORM."""
     return (dgemm_plan_has_m(M, "tail") or any(k[0] == M for k in _plan_accnorm)
             or any(k[0] == M and k[3] == "tail" and v is not None
-                   for k, v in _plan_w8_dg.items())
-            or any(k[0] == M and k[3] == "tail" and v is not None
-                   for k, v in _plan_w4_dg.items()))
+                   for q in (W8, W4) for k, v in q.plan_dg.items()))
 
 
 def accnorm_plan() -> dict:

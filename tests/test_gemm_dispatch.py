@@ -63,6 +63,30 @@ def test_packed_weight_cache_drops_dead_weights():
     assert len(gemm._packed) == n - 1
 
 
+def test_packed_weight_cache_keeps_an_extra_and_checks_the_dtype():
+    """The one registry also holds the quantised weights' packed copies: an entry's
+    ``extra`` (fp8's tile-order row scales) comes back with it, a tensor of another dtype at
+    the same address and shape is not the packed weight, and the entry dies with its weight."""
+    import gc
+    w = torch.zeros(4, 8, dtype=torch.float32)
+    packed, extra = torch.ones(3), torch.arange(4.0)
+    n = len(gemm._packed)
+    gemm._packed_put(w, True, packed, extra)
+    e = gemm._packed_entry(w, True)
+    assert e is not None and e[1] is packed and e[2] is extra
+    assert gemm._packed_get(w, True) is packed and gemm._packed_entry(w, False) is None
+    other = w.view(torch.int32)        # same address and shape, another dtype
+    assert other.data_ptr() == w.data_ptr() and other.shape == w.shape
+    assert gemm._packed_entry(other, True) is None and gemm._packed_get(other, True) is None
+    assert gemm._packed_entry(w, True)[2] is extra      # ... and does not evict the entry
+    gemm._packed_put(other, False, packed)
+    assert gemm._packed_entry(other, False)[2] is None  # no extra unless one is given
+    assert len(gemm._packed) == n + 2
+    del w, other, e
+    gc.collect()
+    assert len(gemm._packed) == n
+
+
 def test_rs_plan_rejects_producers_with_too_many_row_partials():
     """the norm-free layer's consumer (SK_RSCALE, ssl[16][256] in LDS)
     sums at most 256 sum-of-squares partials per row, and the producer leaves

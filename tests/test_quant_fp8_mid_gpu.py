@@ -243,11 +243,11 @@ def test_dispatcher_takes_the_plan_and_falls_back(gpu):
         gemm.linear(x, w8)
         gemm._plan_w8_dg[(M, N, K, "plain")] = (2, 1)
         gemm.linear(x[:80], w8)
-        mode, gemm.w8_dgemm_mode = gemm.w8_dgemm_mode, "0"
+        mode, gemm.W8.dgemm_mode = gemm.W8.dgemm_mode, "0"
         try:
             gemm.linear(x, w8)
         finally:
-            gemm.w8_dgemm_mode = mode
+            gemm.W8.dgemm_mode = mode
         c4 = gemm.w8_counts()
         assert c4["k9mq"] == c3["k9mq"] and c4["widen"] == c3["widen"] + 3
         gemm.clear_plan()
@@ -324,12 +324,12 @@ def test_quantized_engine_at_a_mid_bucket(gpu):
     params = [SamplingParams(temperature=1.0, seed=i, max_tokens=6, ignore_eos=True)
               for i in range(len(prompts))]
     outs = {}
-    mode = gemm.w8_dgemm_mode
+    mode = gemm.W8.dgemm_mode
     try:
         for name, knob, eager in (("graph", "force", False), ("eager", "force", True),
                                   ("off", "0", False)):
             gemm.clear_plan()
-            gemm.w8_dgemm_mode = knob
+            gemm.W8.dgemm_mode = knob
             c0 = gemm.w8_counts()      # (a graph engine's GEMM calls are counted at capture)
             eng = _tiny_engine(enforce_eager=eager, quantization="fp8", max_num_seqs=96,
                                cuda_graph_max_bs=128)
@@ -346,7 +346,7 @@ def test_quantized_engine_at_a_mid_bucket(gpu):
             del eng
             torch.cuda.empty_cache()
     finally:
-        gemm.w8_dgemm_mode = mode
+        gemm.W8.dgemm_mode = mode
         gemm.clear_plan()
     assert all(len(o) == 6 for v in outs.values() for o in v)
     for a, b in zip(outs["graph"], outs["eager"]):
@@ -366,7 +366,7 @@ from kubernetes_gpu_cluster_amd.engine.llm_engine import LLMEngine
 from kubernetes_gpu_cluster_amd.engine.sequence import SamplingParams
 from kubernetes_gpu_cluster_amd.models import PRESETS
 from kubernetes_gpu_cluster_amd.ops import gemm
-assert gemm.w8_dgemm_mode == "force"
+assert gemm.W8.dgemm_mode == "force"
 PRESETS["llama-3-8b-2l"] = PRESETS["llama-3-8b"].shrink(name="llama-3-8b-2l", num_layers=2)
 eng = LLMEngine(EngineConfig(model="llama-3-8b-2l", random_init=True, max_model_len=1024,
                              max_num_seqs=96, max_num_batched_tokens=2048,

@@ -190,11 +190,15 @@ def test_quantized_logits_match_hf_on_dequantized_weights(name):
     model, runner = _ours(cfg, sd)
     shapes = {(i, j): tuple(m.weight.shape) for i, l in enumerate(model.layers)
               for j, m in enumerate(dense_projections(l))}
+    l0 = model.layers[0]
+    tails = {tuple(l0.self_attn.o_proj.weight.shape), tuple(l0.mlp.down_proj.weight.shape)}
     quantize_model(model, "mxfp4")
     assert model.quantization == "mxfp4"
     assert model.fold_rs_weights() == 0 and not model._fusable
     assert not model.silu_weights() and not model.silu_shapes() and not model.tail_shapes()
-    assert not model.fused_norm_shapes() and not model.qkv_dims() and not model.w8_tail_shapes()
+    assert not model.fused_norm_shapes() and not model.qkv_dims()
+    # the quantised tail shapes are the layer's (N, K), not the stored [N, K/2] code bytes
+    assert model.quant_tail_shapes() == tails
     # the four projections of every layer hold codes [N, K/2] + scales [N, K/32]
     for i, l in enumerate(model.layers):
         for j, m in enumerate(dense_projections(l)):

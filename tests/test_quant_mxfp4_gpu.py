@@ -288,12 +288,12 @@ def test_dispatcher_routes(gpu, monkeypatch):
         (_, r), d4, d8 = moved(lambda: gemm.linear_add_rms(x, w4, res, gam, 1e-5))
         assert d4 == {"k9f": 1} and not d8
         torch.testing.assert_close(r.float().cpu(), exp, **TOL)
-        monkeypatch.setattr(gemm, "_w4_enabled", False)         # KGC_W4_GEMM=0
+        monkeypatch.setattr(gemm.W4, "enabled", False)          # KGC_W4_GEMM=0
         y, d4, d8 = moved(lambda: gemm.linear(x, w4))
         assert d4 == {"widen": 1} and not d8
         y, d4, d8 = moved(lambda: gemm.linear_silu(x, w4))
         assert d4 == {"widen": 1} and not d8
-        monkeypatch.setattr(gemm, "_w4_enabled", True)
+        monkeypatch.setattr(gemm.W4, "enabled", True)
         # fp8 and bf16 weights take their old routes
         w8, s8 = quantize_fp8_rows(torch.randn(N, K, dtype=dt, device=gpu) * K ** -0.5)
         _, d4, d8 = moved(lambda: gemm.linear(x, w8))

@@ -298,11 +298,11 @@ def test_dispatcher_takes_the_plan_and_falls_back(gpu):
         gemm.linear(x, w4)
         gemm._plan_w4_dg[(M, N, K, "plain")] = (2, 1)
         gemm.linear(x[:80], w4)
-        mode, gemm.w4_dgemm_mode = gemm.w4_dgemm_mode, "0"
+        mode, gemm.W4.dgemm_mode = gemm.W4.dgemm_mode, "0"
         try:
             gemm.linear(x, w4)
         finally:
-            gemm.w4_dgemm_mode = mode
+            gemm.W4.dgemm_mode = mode
         c4 = gemm.w4_counts()
         assert c4["k9mf"] == c3["k9mf"] and c4["widen"] == c3["widen"] + 3
         gemm.clear_plan()
@@ -320,10 +320,10 @@ def test_tuner_plans_only_packed_weights(gpu):
     from kubernetes_gpu_cluster_amd.ops import gemm
     dt = torch.bfloat16
     w4, sc, _ = _weight(512, 1024, dt, gpu, seed=6)
-    mode = gemm.w4_dgemm_mode
+    mode = gemm.W4.dgemm_mode
     gemm.clear_plan()
     try:
-        gemm.w4_dgemm_mode = "force"
+        gemm.W4.dgemm_mode = "force"
         res = gemm.tune_w4([w4], [4, 128], dt, reps=1)
         assert set(res) == {(4, 512, 1024)} and set(gemm.w4_plan()) == {(4, 512, 1024)}
         assert not gemm.w4_dg_plan() and gemm.w4_packed_weight(w4) is None
@@ -334,7 +334,7 @@ def test_tuner_plans_only_packed_weights(gpu):
         assert set(gemm.w4_plan()) == {(4, 512, 1024)}
         assert gemm.tail_plan_has_m(128) and not gemm.tail_plan_has_m(4)
     finally:
-        gemm.w4_dgemm_mode = mode
+        gemm.W4.dgemm_mode = mode
         gemm.clear_plan()
 
 
@@ -401,12 +401,12 @@ def test_quantized_engine_at_a_mid_bucket(gpu):
     params = [SamplingParams(temperature=1.0, seed=i, max_tokens=6, ignore_eos=True)
               for i in range(len(prompts))]
     outs = {}
-    mode = gemm.w4_dgemm_mode
+    mode = gemm.W4.dgemm_mode
     try:
         for name, knob, eager in (("graph", "force", False), ("eager", "force", True),
                                   ("off", "0", False)):
             gemm.clear_plan()
-            gemm.w4_dgemm_mode = knob
+            gemm.W4.dgemm_mode = knob
             c0 = gemm.w4_counts()      # (a graph engine's GEMM calls are counted at capture)
             eng = _tiny_engine(enforce_eager=eager, quantization="mxfp4", max_num_seqs=96,
                                cuda_graph_max_bs=128)
@@ -427,7 +427,7 @@ def test_quantized_engine_at_a_mid_bucket(gpu):
             del eng, layers, packed
             torch.cuda.empty_cache()
     finally:
-        gemm.w4_dgemm_mode = mode
+        gemm.W4.dgemm_mode = mode
         gemm.clear_plan()
     assert all(len(o) == 6 for v in outs.values() for o in v)
     for a, b in zip(outs["graph"], outs["eager"]):
@@ -447,7 +447,7 @@ from kubernetes_gpu_cluster_amd.engine.llm_engine import LLMEngine
 from kubernetes_gpu_cluster_amd.engine.sequence import SamplingParams
 from kubernetes_gpu_cluster_amd.models import PRESETS
 from kubernetes_gpu_cluster_amd.ops import gemm
-assert gemm.w4_dgemm_mode == "force"
+assert gemm.W4.dgemm_mode == "force"
 PRESETS["llama-3-8b-2l"] = PRESETS["llama-3-8b"].shrink(name="llama-3-8b-2l", num_layers=2)
 eng = LLMEngine(EngineConfig(model="llama-3-8b-2l", random_init=True, max_model_len=1024,
                              max_num_seqs=96, max_num_batched_tokens=2048,

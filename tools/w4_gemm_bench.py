@@ -111,7 +111,7 @@ def main():
             gemm.pack_w8_decode_weights([] if silu else q8[:nb], q8[:nb] if silu else [])
             p4 = [gemm.w4_packed_weight(w, silu) for w in q4[:nb]]
             p8 = [gemm.w8_packed_weight(w, silu) for w in q8[:nb]]
-            s8 = [gemm._q_packed_entry(w, silu)[2] if silu else w.w8_scale for w in q8[:nb]]
+            s8 = [gemm._packed_entry(w, silu)[2] if silu else w.w8_scale for w in q8[:nb]]
         for M in mid:
             x = torch.randn(M, K, dtype=dt, device=dev)
             No = N // 2 if silu else N
