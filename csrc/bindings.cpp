@@ -484,6 +484,86 @@ void plp_merge(Tensor tok_lp, Tensor top_lp, Tensor top_id, std::optional<Tensor
                         (int)R, (int)N, (int)k, stream());
 }
 
+// ---- K16 logits processing
+int64_t lp_chunk(int64_t R, int64_t V) { return kgc::lp_chunk((int)R, (int)V); }
+
+void lp_check_table(const Tensor& ref, const Tensor& table, int64_t R, int64_t nb) {
+  check_same_dev(ref, table, "table");
+  TORCH_CHECK(R >= 0 && R <= 65535 && nb >= 0 && nb < (1 << 28), "kgc.lp: R rows, nb bias entries");
+  TORCH_CHECK(table.scalar_type() == at::kInt && table.is_contiguous() &&
+              table.numel() == 8 * R + 1 + 2 * nb, "kgc.lp: table int32 [8R + 1 + 2nb]");
+}
+
+void lp_check_stats(const Tensor& ref, const Tensor& stats, int64_t V) {
+  check_same_dev(ref, stats, "stats");
+  TORCH_CHECK(stats.scalar_type() == at::kInt && stats.is_contiguous() && stats.dim() == 2 &&
+              stats.size(1) == V && stats.size(0) < INT32_MAX, "kgc.lp: stats int32 [slots, V]");
+}
+
+// in place on the table's rows of logits [S, >= V] (any row stride / element offset)
+void lp_apply(Tensor logits, std::optional<Tensor> stats, Tensor table, int64_t R, int64_t nb,
+              int64_t V, int64_t chunk, std::optional<Tensor> pmax) {
+  check_gpu(logits, "logits");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  TORCH_CHECK(logits.dim() == 2 && (logits.size(1) <= 1 || logits.stride(1) == 1),
+              "kgc.lp_apply: logits [S, V] with dense rows");
+  const int64_t S = logits.size(0);
+  TORCH_CHECK(V >= 0 && V <= logits.size(1) && V < INT32_MAX - kgc::lp_cap() && S < INT32_MAX,
+              "kgc.lp_apply: V out of range");
+  TORCH_CHECK(logits.stride(0) >= 0 && (S <= 1 || logits.stride(0) >= V),
+              "kgc.lp_apply: overlapping rows");
+  lp_check_table(logits, table, R, nb);
+  TORCH_CHECK(chunk >= 1 && chunk <= kgc::lp_cap(), "kgc.lp_apply: chunk in 1..", kgc::lp_cap());
+  const int64_t nsl = (V + chunk - 1) / chunk;
+  TORCH_CHECK(nsl < INT32_MAX, "kgc.lp_apply: too many slices");
+  const uint32_t* sp = nullptr;
+  int64_t nslots = 0;
+  if (stats.has_value()) {
+    lp_check_stats(logits, *stats, V);
+    sp = reinterpret_cast<const uint32_t*>(stats->data_ptr<int>());
+    nslots = stats->size(0);
+  }
+  float* pm = nullptr;
+  if (pmax.has_value()) {
+    check_same_dev(logits, *pmax, "pmax");
+    TORCH_CHECK(pmax->scalar_type() == at::kFloat && pmax->is_contiguous() &&
+                pmax->numel() >= R * nsl, "kgc.lp_apply: pmax fp32 [R, slices]");
+    pm = pmax->data_ptr<float>();
+  }
+  if (R == 0 || V == 0) return;
+  kgc::launch_lp_apply(dt_code(logits), logits.data_ptr(), logits.stride(0), (int)S, sp,
+                       (int)nslots, table.data_ptr<int>(), (int)R, (int)nb, (int)V, (int)chunk,
+                       pm != nullptr, pm, stream());
+}
+
+void lp_update(Tensor stats, Tensor table, int64_t R, int64_t nb, Tensor sampled) {
+  check_gpu(stats, "stats");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(stats.device());
+  lp_check_stats(stats, stats, stats.dim() == 2 ? stats.size(1) : -1);
+  TORCH_CHECK(stats.size(1) >= 1, "kgc.lp_update: empty vocabulary");
+  lp_check_table(stats, table, R, nb);
+  check_same_dev(stats, sampled, "sampled");
+  TORCH_CHECK(sampled.scalar_type() == at::kLong && sampled.is_contiguous() &&
+              sampled.numel() < INT32_MAX, "kgc.lp_update: sampled int64 [S]");
+  kgc::launch_lp_update(reinterpret_cast<uint32_t*>(stats.data_ptr<int>()), (int)stats.size(0),
+                        table.data_ptr<int>(), (int)R, sampled.data_ptr<int64_t>(),
+                        (int)sampled.numel(), (int)stats.size(1), stream());
+}
+
+void lp_init(Tensor stats, int64_t slot, Tensor toks, int64_t n_prompt) {
+  check_gpu(stats, "stats");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(stats.device());
+  lp_check_stats(stats, stats, stats.dim() == 2 ? stats.size(1) : -1);
+  TORCH_CHECK(slot >= 0 && slot < stats.size(0), "kgc.lp_init: slot out of range");
+  check_same_dev(stats, toks, "toks");
+  TORCH_CHECK(toks.scalar_type() == at::kInt && toks.is_contiguous() && toks.numel() < INT32_MAX &&
+              n_prompt >= 0 && n_prompt <= toks.numel(), "kgc.lp_init: toks int32 [n], n_prompt <= n");
+  const int64_t V = stats.size(1);
+  if (V == 0) return;
+  kgc::launch_lp_init(reinterpret_cast<uint32_t*>(stats.data_ptr<int>()) + slot * V,
+                      toks.data_ptr<int>(), (int)toks.numel(), (int)n_prompt, (int)V, stream());
+}
+
 // ---- K13/K14 MoE
 void moe_route(Tensor topk_w, Tensor topk_ids, Tensor logits, bool renorm) {
   check_gpu(logits, "logits");
@@ -1633,6 +1713,11 @@ TORCH_LIBRARY(kgc, m) {
         "int k) -> ()");
   m.def("plp_merge(Tensor(a!) tok_lp, Tensor(b!) top_lp, Tensor(c!) top_id, Tensor(d!)? out_rec, "
         "Tensor rec, int k) -> ()");
+  m.def("lp_chunk(int R, int V) -> int", &lp_chunk);
+  m.def("lp_apply(Tensor(a!) logits, Tensor? stats, Tensor table, int R, int nb, int V, int chunk, "
+        "Tensor(b!)? pmax) -> ()");
+  m.def("lp_update(Tensor(a!) stats, Tensor table, int R, int nb, Tensor sampled) -> ()");
+  m.def("lp_init(Tensor(a!) stats, int slot, Tensor toks, int n_prompt) -> ()");
   m.def("decode_wave_min_pairs() -> int", &decode_wave_min_pairs);
   m.def("moe_route(Tensor(a!) topk_w, Tensor(b!) topk_ids, Tensor logits, bool renorm) -> ()");
   m.def("moe_gate_route(Tensor(a!) topk_w, Tensor(b!) topk_ids, Tensor x, Tensor wg, "
@@ -1740,6 +1825,9 @@ TORCH_LIBRARY_IMPL(kgc, CUDA, m) {
   m.impl("sample_vp_unpack", &sample_vp_unpack);
   m.impl("plp_partial", &plp_partial);
   m.impl("plp_merge", &plp_merge);
+  m.impl("lp_apply", &lp_apply);
+  m.impl("lp_update", &lp_update);
+  m.impl("lp_init", &lp_init);
   m.impl("xgmi_allreduce", &xgmi_allreduce);
   m.impl("xgmi_allreduce_rms", &xgmi_allreduce_rms);
   m.impl("xgmi_allreduce_emu", &xgmi_allreduce_emu);

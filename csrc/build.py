@@ -39,6 +39,10 @@ def _paths(debug: bool) -> tuple[str, str]:
 
 OUT, BUILD = _paths(DEBUG)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+# per-file flags.  New kernels are compiled without the packed fp32 instructions
+# (v_pk_add / mul / fma_f32); the older files keep the flags their numbers were taken with.
+NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+EXTRA_FLAGS = {"logits_process.hip": NO_PK_F32}
 
 
 def _torch_paths():
@@ -75,7 +79,8 @@ def build(force: bool = False, jobs: int = 8, arch: str = "gfx950", verbose: boo
     jobs_list = []
     for src in kern:
         obj = os.path.join(BUILD, os.path.basename(src) + ".o")
-        jobs_list.append((src, obj, ["-x", "hip"] + common))
+        jobs_list.append((src, obj, ["-x", "hip"] + common +
+                          EXTRA_FLAGS.get(os.path.basename(src), [])))
     bind = os.path.join(CSRC, "bindings.cpp")
     bobj = os.path.join(BUILD, "bindings.o")
     bflags = ["-x", "hip", "-O2", "-fPIC", "-std=c++17", f"--offload-arch={arch}", "-I", CSRC,

@@ -106,6 +106,20 @@ void launch_plp_partial(int dtype, float* rec, const void* logits, int64_t row_s
 void launch_plp_merge(float* tok_lp, float* top_lp, int* top_id, float* out_rec, const float* rec,
                       int R, int N, int k, hipStream_t s);
 
+// K16 logits processing (logits_process.hip).  tab: the step's int32 table of R rows and nb
+// bias entries (layout in the kernel file); stats: uint32 [nslots, V] or nullptr; chunk <=
+// lp_cap() columns per workgroup (lp_chunk picks one); pmax: fp32 [R, ceil(V / chunk)]
+// when any_minp.  launch_lp_init zeroes the slot's row srow [V] and counts toks [n]: the
+// first n_prompt as prompt tokens, the rest as generated ones.
+int lp_cap();
+int lp_chunk(int R, int V);
+void launch_lp_apply(int dtype, void* logits, int64_t row_stride, int S, const uint32_t* stats,
+                     int nslots, const int* tab, int R, int nb, int V, int chunk, bool any_minp,
+                     float* pmax, hipStream_t s);
+void launch_lp_update(uint32_t* stats, int nslots, const int* tab, int R, const int64_t* sampled,
+                      int S, int V, hipStream_t s);
+void launch_lp_init(uint32_t* srow, const int* toks, int n, int n_prompt, int V, hipStream_t s);
+
 // K9 skinny (small-M decode) GEMM: C[M, N] = X[M, K] . W[N, K]^T (+ bias), M <= 16*mt.
 // epi: 0 plain, 1 RMS-normalise X rows on the fly (gamma [K], eps), 2 accumulate into C,
 // 3 silu(gate) * up over a merged weight (C [M, N/2]), 4 accumulate into C then

@@ -7,17 +7,25 @@
 * ``min_p``: drop tokens whose probability is below ``min_p`` x the top probability.
 
 Only the rows of requests that use one of these are touched, so the common path
-(none used) costs nothing.  Token statistics live on the device: one int32 count row
-and one prompt bitmap row per running-sequence slot.  They are allocated on first use
-and updated with a scatter after each sampling step, so the host never walks token
-lists for a decode step.  A sequence (re)entering a slot, on admission or after
-recompute preemption, has its row rebuilt from its token lists.
+(none used) costs nothing.  Token statistics live on the device, one row per
+running-sequence slot.  They are allocated on first use and updated after each sampling
+step, so the host never walks token lists for a decode step.  A sequence (re)entering a
+slot, on admission or after recompute preemption, has its row rebuilt from its token lists.
+
+On a GPU all of it runs on the K16 HIP kernels (``ops.logits_process``,
+``ops.token_stats_update``, ``ops.token_stats_init``): one packed int32 word per (slot,
+token) -- bit 31 "in the prompt", low bits the generated count -- and one pinned parameter
+block per step, copied without a host wait.  ``KGC_LOGITS_KERNEL=0`` keeps the torch
+formulation below (an int32 count row and a prompt bitmap row per slot) on the GPU; on
+the CPU it is the only path.
 """
 from __future__ import annotations
 
 from typing import Optional
 
 import torch
+
+from .. import ops
 
 
 def needs_processing(p) -> bool:
@@ -34,9 +42,16 @@ class LogitsProcessor:
         self.max_seqs, self.vocab, self.device = max_seqs, vocab, device
         self.counts: Optional[torch.Tensor] = None      # [slots, V] int32: generated tokens
         self.prompt_mask: Optional[torch.Tensor] = None  # [slots, V] bool: prompt tokens
+        self.kernel = device.type == "cuda" and ops.logits_kernel_enabled()
+        self.stats: Optional[torch.Tensor] = None       # K16: [slots, V] int32 packed words
+        self._table = (None, None)                      # (the rows list, its LogitsTable)
 
     def _ensure(self) -> None:
-        if self.counts is None:
+        if self.kernel:
+            if self.stats is None:
+                self.stats = torch.zeros(self.max_seqs, self.vocab, dtype=torch.int32,
+                                         device=self.device)
+        elif self.counts is None:
             self.counts = torch.zeros(self.max_seqs, self.vocab, dtype=torch.int32, device=self.device)
             self.prompt_mask = torch.zeros(self.max_seqs, self.vocab, dtype=torch.bool,
                                            device=self.device)
@@ -44,6 +59,9 @@ class LogitsProcessor:
     def init_slot(self, slot: int, prompt: list[int], output: list[int]) -> None:
         """(Re)build a slot's statistics from the sequence's token lists."""
         self._ensure()
+        if self.kernel:
+            ops.token_stats_init(self.stats, slot, prompt, [t for t in output if t >= 0])
+            return
         self.counts[slot].zero_()
         self.prompt_mask[slot].zero_()
         if prompt:
@@ -53,9 +71,31 @@ class LogitsProcessor:
             idx = torch.tensor(out, device=self.device)
             self.counts[slot].index_add_(0, idx, torch.ones_like(idx, dtype=torch.int32))
 
+    def _step_table(self, rows: list[tuple]) -> "ops.LogitsTable":
+        """The step's parameter table; ``update`` reuses the one ``apply`` built for the
+        same rows list."""
+        if self._table[0] is rows:
+            return self._table[1]
+        ps = [x[2] for x in rows]
+        slots = [x[1] if needs_counts(x[2]) else -1 for x in rows]
+        if any(s >= 0 for s in slots):
+            self._ensure()
+        table = ops.logits_table(
+            [x[0] for x in rows], slots, [p.presence_penalty for p in ps],
+            [p.frequency_penalty for p in ps], [p.repetition_penalty for p in ps],
+            [p.min_p for p in ps],
+            [max(p.temperature, 1e-5) if p.temperature > 0 else 1.0 for p in ps],
+            [[(int(k), float(v)) for k, v in p.logit_bias.items()] if p.logit_bias else []
+             for p in ps], self.device)
+        self._table = (rows, table)
+        return table
+
     def apply(self, logits: torch.Tensor, rows: list[tuple]) -> None:
         """In place on ``logits`` [S, V]; rows = [(row, slot, SamplingParams)]."""
         V = min(logits.shape[-1], self.vocab)
+        if self.kernel:
+            ops.logits_process(logits, self.stats, self._step_table(rows), V)
+            return
         dev = logits.device
         r = torch.tensor([x[0] for x in rows], device=dev)
         sub = logits.index_select(0, r).float()
@@ -94,6 +134,11 @@ class LogitsProcessor:
 
     def update(self, rows: list[tuple], sampled: torch.Tensor) -> None:
         """Count each penalised row's new token (device scatter, no host sync)."""
+        if self.kernel:
+            table = self._step_table(rows)
+            if table.any_slot:
+                ops.token_stats_update(self.stats, table, sampled)
+            return
         pen = [(x[0], x[1]) for x in rows if needs_counts(x[2])]
         if not pen:
             return

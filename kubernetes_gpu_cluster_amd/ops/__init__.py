@@ -11,6 +11,7 @@ import math
 import os
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import reference as ref
@@ -492,6 +493,90 @@ def prompt_logprobs(logits: torch.Tensor, targets: torch.Tensor, k: int = 0, voc
     """log-softmax value of ``targets`` and the k best columns of each row of ``logits``
     (one rank holding the whole vocabulary): stage 1 then stage 2."""
     return prompt_logprobs_merge(prompt_logprobs_partial(logits, targets, vocab_off, ncols, k), k)
+
+
+# ------------------------------------------------------------------ logits processing (K16)
+def logits_kernel_enabled() -> bool:
+    """KGC_LOGITS_KERNEL=0: the engine's LogitsProcessor keeps its torch path on the GPU."""
+    return os.environ.get("KGC_LOGITS_KERNEL", "1") != "0"
+
+
+def _staged(words: np.ndarray, device) -> torch.Tensor:
+    """int32 words -> ``device``.  GPU: through a fresh pinned block and one non-blocking
+    copy; the caching host allocator keeps the block until the copy has run, so the caller
+    never waits and may run a step ahead."""
+    if torch.device(device).type != "cuda":
+        return torch.from_numpy(np.ascontiguousarray(words, dtype=np.int32))
+    host = torch.empty(words.size, dtype=torch.int32, pin_memory=True)
+    host.numpy()[:] = words
+    return host.to(device, non_blocking=True)
+
+
+class LogitsTable:
+    """One step's per-row parameters for ``logits_process`` / ``token_stats_update``, as one
+    int32 block on the device (floats as their bits):
+    row[R] slot[R] pres[R] freq[R] rep[R] min_p[R] t[R] off[R + 1] ids[nb] vals[nb]."""
+    __slots__ = ("data", "R", "nb", "any_minp", "any_slot")
+
+    def __init__(self, data, R, nb, any_minp, any_slot):
+        self.data, self.R, self.nb, self.any_minp, self.any_slot = data, R, nb, any_minp, any_slot
+
+
+def logits_table(rows, slots, pres, freq, rep, min_p, temp, bias, device) -> LogitsTable:
+    """Pack the table.  Per processed row: its logits row, its statistics slot (-1: the row
+    has no penalties), presence / frequency / repetition penalty, min_p (0: off) and the
+    temperature min_p divides by; ``bias``: per row a list of (token id, value)."""
+    R = len(rows)
+    off = np.zeros(R + 1, dtype=np.int32)
+    off[1:] = np.cumsum([len(b) for b in bias])
+    nb = int(off[-1])
+    flat = [e for b in bias for e in b]
+    f = lambda x: np.asarray(x, dtype=np.float32).view(np.int32)          # noqa: E731
+    words = np.concatenate([np.asarray(rows, dtype=np.int32), np.asarray(slots, dtype=np.int32),
+                            f(pres), f(freq), f(rep), f(min_p), f(temp), off,
+                            np.asarray([e[0] for e in flat], dtype=np.int64).clip(-1, 2**31 - 1)
+                            .astype(np.int32), f([e[1] for e in flat])])
+    return LogitsTable(_staged(words, device), R, nb, any(m > 0 for m in min_p),
+                       any(s >= 0 for s in slots))
+
+
+def logits_process(logits: torch.Tensor, stats: Optional[torch.Tensor], table: LogitsTable,
+                   vocab: Optional[int] = None, chunk: int = 0) -> torch.Tensor:
+    """K16, in place on the table's rows of ``logits`` [S, >= vocab] (bf16 / f16 / fp32, any
+    row stride and element offset), columns [0, vocab): repetition penalty, frequency and
+    presence penalty from ``stats`` (int32 [slots, vocab]: bit 31 "in the prompt", low bits
+    the generated count; None: no row has a slot), logit_bias, min_p -- in that order, in
+    fp32, rounded once.  Other rows and columns >= vocab are not touched.  ``chunk`` = 0: as
+    many columns per workgroup as the kernel chooses."""
+    V = logits.shape[1] if vocab is None else vocab
+    if not _gpu(logits):
+        return ref.logits_process(logits, stats, table.data, table.R, table.nb, V)
+    chunk = chunk or int(_k().lp_chunk(table.R, V))
+    pmax = None
+    if table.any_minp:
+        pmax = torch.empty(table.R * max(1, -(-V // chunk)), dtype=torch.float32,
+                           device=logits.device)
+    _k().lp_apply(logits, stats, table.data, table.R, table.nb, V, chunk, pmax)
+    return logits
+
+
+def token_stats_update(stats: torch.Tensor, table: LogitsTable, sampled: torch.Tensor) -> None:
+    """stats[slot, clamp(sampled[row])] += 1 for the table's rows that have a slot
+    (``sampled`` int64 [S]); no host sync, no host tensor."""
+    if not _gpu(stats):
+        return ref.token_stats_update(stats, table.data, table.R, sampled)
+    _k().lp_update(stats, table.data, table.R, table.nb, sampled)
+
+
+def token_stats_init(stats: torch.Tensor, slot: int, prompt, output) -> None:
+    """(Re)build one slot's statistics row from a sequence's token lists: the row is
+    cleared, prompt tokens set bit 31, generated tokens are counted."""
+    toks = np.concatenate([np.asarray(prompt, dtype=np.int64),
+                           np.asarray(output, dtype=np.int64)]).clip(-1, 2**31 - 1)
+    dev = _staged(toks.astype(np.int32), stats.device)
+    if not _gpu(stats):
+        return ref.token_stats_init(stats, slot, dev, len(prompt))
+    _k().lp_init(stats, slot, dev, len(prompt))
 
 
 __all__ = ["load_extension", "rms_norm", "fused_add_rms_norm", "layer_norm", "silu_mul",

@@ -411,6 +411,57 @@ def prompt_logprobs_merge(rec: torch.Tensor, k: int, as_record: bool = False):
     return lp(T).to(dev), lp(v).to(dev), i.to(dev)
 
 
+# ---------------------------------------------------------------- logits processing (K16)
+LP_PROMPT = -2 ** 31          # bit 31 of the int32 statistics word: "in the prompt"
+LP_COUNT = 2 ** 31 - 1        # low 31 bits: how often the token was generated
+
+
+def _lp_fields(table: torch.Tensor, R: int, nb: int):
+    f = table.view(torch.float32)
+    return (table[:R].tolist(), table[R:2 * R].tolist(), f[2 * R:3 * R].tolist(),
+            f[3 * R:4 * R].tolist(), f[4 * R:5 * R].tolist(), f[5 * R:6 * R].tolist(),
+            f[6 * R:7 * R].tolist(), table[7 * R:8 * R + 1].tolist(),
+            table[8 * R + 1:8 * R + 1 + nb].long(), f[8 * R + 1 + nb:8 * R + 1 + 2 * nb])
+
+
+def logits_process(logits: torch.Tensor, stats: Optional[torch.Tensor], table: torch.Tensor,
+                   R: int, nb: int, V: int) -> torch.Tensor:
+    """The torch formulation of K16 over the packed statistics word, row by row, in place."""
+    rows, slots, pres, freq, rep, minp, temp, off, ids, vals = _lp_fields(table, R, nb)
+    for j, r in enumerate(rows):
+        s = logits[r, :V].float()
+        if stats is not None and slots[j] >= 0:
+            w = stats[slots[j], :V]
+            cnt, seen = (w & LP_COUNT).float(), w != 0
+            s = torch.where(seen & (s > 0), s / rep[j], torch.where(seen, s * rep[j], s))
+            s = s - freq[j] * cnt - pres[j] * (cnt > 0).float()
+        i, v = ids[off[j]:off[j + 1]], vals[off[j]:off[j + 1]]
+        ok = (i >= 0) & (i < V)
+        s.index_add_(0, i[ok], v[ok])
+        if minp[j] > 0:
+            prob = torch.softmax(s / temp[j], dim=-1)
+            s = torch.where(prob >= minp[j] * prob.max(), s, torch.full_like(s, _NEG_INF))
+        logits[r, :V] = s.to(logits.dtype)
+    return logits
+
+
+def token_stats_update(stats: torch.Tensor, table: torch.Tensor, R: int,
+                       sampled: torch.Tensor) -> None:
+    rows, slots = table[:R].long(), table[R:2 * R].long()
+    has = slots >= 0
+    tok = sampled.index_select(0, rows[has]).clamp(0, stats.shape[1] - 1)
+    stats.index_put_((slots[has], tok), torch.ones_like(tok, dtype=torch.int32), accumulate=True)
+
+
+def token_stats_init(stats: torch.Tensor, slot: int, toks: torch.Tensor, n_prompt: int) -> None:
+    row = stats[slot].zero_()
+    toks = toks.long()
+    ok = (toks >= 0) & (toks < stats.shape[1])
+    p, o = toks[:n_prompt][ok[:n_prompt]], toks[n_prompt:][ok[n_prompt:]]
+    row[p] = LP_PROMPT
+    row.index_add_(0, o, torch.ones_like(o, dtype=torch.int32))
+
+
 # ---------------------------------------------------------------- MoE
 def moe_topk_softmax(router_logits: torch.Tensor, k: int, renormalize: bool = True):
     """K13: softmax over experts, top-k; returns (weights fp32 [T,k], ids int32 [T,k])."""
