@@ -1577,6 +1577,86 @@ std::vector<int64_t> w8_dgemm_cfg_info(int64_t cfg) {
   return {bm, bn, ns};
 }
 
+// K9a (gemm_w8a8.hip): xq [M, K] e4m3, xs [M] fp32 <- per-row dynamic quantisation of x
+void act_quant_fp8(Tensor xq, Tensor xs, Tensor x) {
+  check_gpu(x, "x");
+  check_same_dev(x, xq, "xq");
+  check_same_dev(x, xs, "xs");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf,
+              "kgc.act_quant_fp8: bf16/f16 x");
+  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0 &&
+              x.stride(0) >= x.size(1) && reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "kgc.act_quant_fp8: x [M, K], row stride a multiple of 8, 16-B aligned");
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(K >= 16 && K % 16 == 0 && K <= kgc::act_quant_fp8_max_k() && M <= INT32_MAX,
+              "kgc.act_quant_fp8: K % 16 == 0, K <= 16384");
+  TORCH_CHECK(xq.scalar_type() == at::kFloat8_e4m3fn && xq.dim() == 2 && xq.is_contiguous() &&
+              xq.size(0) == M && xq.size(1) == K &&
+              reinterpret_cast<uintptr_t>(xq.data_ptr()) % 16 == 0,
+              "kgc.act_quant_fp8: xq [M, K] float8_e4m3fn contiguous, 16-B aligned");
+  TORCH_CHECK(xs.scalar_type() == at::kFloat && xs.is_contiguous() && xs.dim() == 1 &&
+              xs.numel() == M, "kgc.act_quant_fp8: xs fp32 [M]");
+  kgc::launch_act_quant_fp8(dt_code(x), xq.data_ptr(), xs.data_ptr<float>(), x.data_ptr(), (int)M,
+                            (int)K, x.stride(0), stream());
+}
+
+// K9a (gemm_w8a8.hip): out [M, N] = (xq . w8^T) * xs[m] * ws[n] (+ bias), e4m3 x e4m3 MFMA
+void w8a8_gemm(Tensor out, Tensor xq, Tensor xs, Tensor w8, Tensor ws, std::optional<Tensor> bias,
+               int64_t cfg) {
+  check_gpu(xq, "xq");
+  check_same_dev(xq, out, "out");
+  check_same_dev(xq, xs, "xs");
+  check_same_dev(xq, w8, "w8");
+  check_same_dev(xq, ws, "ws");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(xq.device());
+  TORCH_CHECK(cfg >= 0 && cfg < kgc::w8a8_gemm_num_cfgs(), "kgc.w8a8_gemm: unknown tile config");
+  TORCH_CHECK(out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kHalf,
+              "kgc.w8a8_gemm: bf16/f16 out");
+  TORCH_CHECK(xq.scalar_type() == at::kFloat8_e4m3fn && xq.dim() == 2 && xq.is_contiguous() &&
+              reinterpret_cast<uintptr_t>(xq.data_ptr()) % 16 == 0,
+              "kgc.w8a8_gemm: xq [M, K] float8_e4m3fn contiguous, 16-B aligned");
+  TORCH_CHECK(w8.scalar_type() == at::kFloat8_e4m3fn && w8.dim() == 2 && w8.is_contiguous() &&
+              reinterpret_cast<uintptr_t>(w8.data_ptr()) % 16 == 0,
+              "kgc.w8a8_gemm: w8 [N, K] float8_e4m3fn contiguous, 16-B aligned");
+  const int64_t M = xq.size(0), K = xq.size(1), N = w8.size(0);
+  TORCH_CHECK(w8.size(1) == K, "kgc.w8a8_gemm: xq [M, K] and w8 [N, K] disagree on K");
+  TORCH_CHECK(M >= 1 && N >= 128 && N % 128 == 0 && K >= 128 && K % 128 == 0,
+              "kgc.w8a8_gemm: M >= 1, N % 128 == 0, K % 128 == 0");
+  TORCH_CHECK(M < ((int64_t)1 << 31) - 256 && N < ((int64_t)1 << 31) - 256 &&
+              K < ((int64_t)1 << 31), "kgc.w8a8_gemm: size limits");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == M && out.size(1) == N && out.stride(1) == 1 &&
+              out.stride(0) % 8 == 0 && out.stride(0) >= N &&
+              reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0,
+              "kgc.w8a8_gemm: out [M, N], row stride a multiple of 8, 16-B aligned");
+  TORCH_CHECK(xs.scalar_type() == at::kFloat && xs.is_contiguous() && xs.dim() == 1 &&
+              xs.numel() == M, "kgc.w8a8_gemm: xs fp32 [M]");
+  TORCH_CHECK(ws.scalar_type() == at::kFloat && ws.is_contiguous() && ws.numel() == N,
+              "kgc.w8a8_gemm: ws fp32 [N]");
+  int bm, bn, ns;
+  kgc::w8a8_gemm_cfg_info((int)cfg, &bm, &bn, &ns);
+  TORCH_CHECK(((M + bm - 1) / bm) * ((N + bn - 1) / bn) < ((int64_t)1 << 31),
+              "kgc.w8a8_gemm: grid too large");
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_contiguous() && bias->numel() == N &&
+                bias->scalar_type() == out.scalar_type(), "kgc.w8a8_gemm: bias [N] in out's dtype");
+    check_same_dev(xq, *bias, "bias");
+    bp = bias->data_ptr();
+  }
+  kgc::launch_w8a8_gemm(dt_code(out), (int)cfg, out.data_ptr(), xq.data_ptr(),
+                        xs.data_ptr<float>(), w8.data_ptr(), ws.data_ptr<float>(), bp, (int)M,
+                        (int)N, (int)K, out.stride(0), stream());
+}
+
+int64_t w8a8_gemm_num_cfgs() { return kgc::w8a8_gemm_num_cfgs(); }
+std::vector<int64_t> w8a8_gemm_cfg_info(int64_t cfg) {
+  TORCH_CHECK(cfg >= 0 && cfg < kgc::w8a8_gemm_num_cfgs(), "kgc.w8a8_gemm: unknown tile config");
+  int bm, bn, ns;
+  kgc::w8a8_gemm_cfg_info((int)cfg, &bm, &bn, &ns);
+  return {bm, bn, ns};
+}
+
 // K9mf (gemm_w4_decode.hip): the K9m pipeline over packed MXFP4 weights Wp [N/128, K/64, 4352]
 // (w4_dgemm_pack).  out fp32 [S, M, N] (epi 0), [M, N] (epi 1) or [M, N/2] (epi 2) in X's dtype.
 void w4_dgemm(Tensor C, Tensor X, Tensor Wp, std::optional<Tensor> bias, int64_t cfg,
@@ -1805,6 +1885,11 @@ TORCH_LIBRARY(kgc, m) {
   m.def("w8_dgemm_pack(Tensor(a!) P, Tensor W8, bool silu) -> ()");
   m.def("w8_dgemm_num_cfgs() -> int", &w8_dgemm_num_cfgs);
   m.def("w8_dgemm_cfg_info(int cfg) -> int[]", &w8_dgemm_cfg_info);
+  m.def("act_quant_fp8(Tensor(a!) xq, Tensor(b!) xs, Tensor x) -> ()");
+  m.def("w8a8_gemm(Tensor(a!) out, Tensor xq, Tensor xs, Tensor w8, Tensor ws, Tensor? bias, "
+        "int cfg) -> ()");
+  m.def("w8a8_gemm_num_cfgs() -> int", &w8a8_gemm_num_cfgs);
+  m.def("w8a8_gemm_cfg_info(int cfg) -> int[]", &w8a8_gemm_cfg_info);
   m.def("w4_dgemm(Tensor(a!) C, Tensor X, Tensor Wp, Tensor? bias, int cfg, int epi) -> ()");
   m.def("w4_dgemm_pack(Tensor(a!) P, Tensor W4, Tensor scales, bool silu) -> ()");
   m.def("w4_dgemm_num_cfgs() -> int", &w4_dgemm_num_cfgs);
@@ -1857,6 +1942,8 @@ TORCH_LIBRARY_IMPL(kgc, CUDA, m) {
   m.impl("w4_widen", &w4_widen);
   m.impl("w8_dgemm", &w8_dgemm);
   m.impl("w8_dgemm_pack", &w8_dgemm_pack);
+  m.impl("act_quant_fp8", &act_quant_fp8);
+  m.impl("w8a8_gemm", &w8a8_gemm);
   m.impl("w4_dgemm", &w4_dgemm);
   m.impl("w4_dgemm_pack", &w4_dgemm_pack);
 }

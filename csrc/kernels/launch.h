@@ -153,6 +153,18 @@ void launch_w8_dgemm(int dtype, int cfg, int epi, void* C, const void* X, const 
                      const float* scale, const void* bias, int M, int N, int K, int64_t ldx,
                      int S, int64_t slice_stride, hipStream_t s);
 void launch_w8_dgemm_pack(bool silu, void* P, const void* W8, int N, int K, hipStream_t s);
+// K9a (gemm_w8a8.hip): per-row dynamic e4m3 quantisation of X [M, K] (Xq [M, K] contiguous,
+// xs fp32 [M]; K % 16 == 0, K <= act_quant_fp8_max_k()), and the fp8 x fp8 MFMA GEMM
+// C [M, N] = (Xq . W8^T) * xs[m] * ws[n] (+ bias) over the row-major e4m3 weight W8 [N, K]
+// in place; N % 128 == 0, K % 128 == 0.  w8a8_gemm_cfg_info: BM, BN, ring slots.
+int w8a8_gemm_num_cfgs();
+void w8a8_gemm_cfg_info(int cfg, int* bm, int* bn, int* ns);
+int act_quant_fp8_max_k();
+void launch_w8a8_gemm(int dtype, int cfg, void* C, const void* Xq, const float* xs,
+                      const void* W8, const float* ws, const void* bias, int M, int N, int K,
+                      int64_t ldc, hipStream_t s);
+void launch_act_quant_fp8(int dtype, void* Xq, float* xs, const void* X, int M, int K,
+                          int64_t ldx, hipStream_t s);
 
 // K9f: weight-only MXFP4 skinny GEMM (gemm_w4.hip) over codes W [N, K/2] (two e2m1 per byte,
 // low nibble first) and e8m0 block scales S [N, K/32], and the exact widening to bf16/f16.

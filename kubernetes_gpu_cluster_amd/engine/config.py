@@ -21,7 +21,7 @@ _DTYPES = {"auto": None, "bfloat16": torch.bfloat16, "bf16": torch.bfloat16,
 
 
 KV_CACHE_DTYPES = ("auto", "bfloat16", "bf16", "float16", "fp16", "fp8", "fp8_e4m3")
-QUANTIZATION_METHODS = ("fp8", "mxfp4")
+QUANTIZATION_METHODS = ("fp8", "mxfp4", "fp8_w8a8")
 
 
 @dataclasses.dataclass
@@ -46,7 +46,7 @@ class EngineConfig:
     disable_custom_all_reduce: bool = False
     trust_remote_code: bool = False
     kv_cache_dtype: str = "auto"
-    quantization: Optional[str] = None    # None | fp8 (W8A16) | mxfp4 (W4A16), models/quant.py
+    quantization: Optional[str] = None    # None | fp8 (W8A16) | mxfp4 (W4A16) | fp8_w8a8, models/quant.py
     seed: int = 0
     random_init: bool = False
     num_gpu_blocks_override: Optional[int] = None
@@ -149,7 +149,11 @@ def add_engine_args(p: argparse.ArgumentParser) -> argparse.ArgumentParser:
            "(W4A16, 4.25 bits per weight) of the same linears: a quarter of the weight bytes "
            "and the K9f GEMM at decode batches <= 64, the K9mf GEMM over packed copies at "
            "decode batches 65-512 (KGC_W4_DGEMM=0: none); prefill takes the widen path; "
-           "less accurate than fp8.  Not for MoE or OPT models")
+           "less accurate than fp8.  fp8_w8a8: fp8's weights and its decode kernels (K9q at "
+           "batches <= 64, K9mq at the tuned buckets), but prefill and every other linear "
+           "above 64 rows quantise the activations per token to e4m3 and run the fp8 x fp8 "
+           "MFMA GEMM K9a on the weight in place instead of the widen path "
+           "(KGC_W8A8_GEMM=0: widen).  Not for MoE or OPT models")
     a("--seed", type=int, default=0)
     a("--random-init", action="store_true", help="random weights (offline benchmarking)")
     a("--load-format", type=str, default="auto", help="'dummy' == --random-init")

@@ -1,5 +1,6 @@
-"""``--quantization fp8 | mxfp4``: online weight-only quantisation (W8A16 / W4A16) of the
-dense Llama-family linears.
+"""``--quantization fp8 | mxfp4 | fp8_w8a8``: online weight-only quantisation (W8A16 /
+W4A16) of the dense Llama-family linears; ``fp8_w8a8`` makes ``fp8``'s weights and marks them
+as taking fp8 activations where the W8A16 kernels do not serve (ops/gemm.py W8A8).
 
 After a rank has loaded its shard, the qkv / o / gate_up / down projection weights of every
 layer are replaced by their e4m3 form with one fp32 scale per output row, or by their MXFP4
@@ -17,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from ..ops.quant import (MXFP4_BLOCK, QUANTIZATION_METHODS, attach_scale, attach_w4_scale, is_fp8,
-                         is_mxfp4, quantize_fp8_rows, quantize_mxfp4)
+                         is_mxfp4, mark_act_fp8, quantize_fp8_rows, quantize_mxfp4)
 from .configs import ModelConfig
 
 log = logging.getLogger("kgc.quant")
@@ -78,6 +79,8 @@ def quantize_model(model: nn.Module, method: str = "fp8") -> int:
                 w8, scale = quantize_fp8_rows(w.data)
                 p = nn.Parameter(w8, requires_grad=False)
                 attach_scale(p, scale)
+                if method == "fp8_w8a8":
+                    mark_act_fp8(p)
             if loader is not None:
                 p.weight_loader = loader  # type: ignore[attr-defined]
             saved += (w.numel() * w.element_size() - w8.numel()

@@ -25,7 +25,7 @@ import torch
 import torch.nn.functional as F
 
 from .quant import (MXFP4_TILE_BYTES, dequantize_fp8_rows, dequantize_mxfp4, is_fp8, is_mxfp4,
-                    tile_rows, w4_scale, w8_scale)
+                    quantize_fp8_rows, takes_act_fp8, tile_rows, w4_scale, w8_scale)
 
 log = logging.getLogger("kgc.gemm")
 
@@ -126,6 +126,20 @@ _PACK_FRACTION = float(os.environ.get("KGC_DGEMM_PACK_FRACTION", "0.25"))
 #            packed e4m3 tiles (one byte per weight element) or packed mxfp4 tiles (0.53).
 # Everything that differs between the two is a ``QuantMethod`` instance (W8, W4 below); the
 # routing, the tuners and the packing are written once, as its methods.
+# A third method, --quantization fp8_w8a8 (W8A8 below), is W8 with one routing difference.
+# Its weights are fp8's, each marked as taking fp8 activations (quant.mark_act_fp8); it has
+# W8's kernels, packing and tuner (its own instance, so its own plans and counters), and
+# M <= 64 and the tuned mid-M buckets run K9q / K9mq exactly as under fp8.  Only where
+# ``linear`` would end in the widen path -- every prefill and mixed step, every M > 64
+# without a K9mq plan entry -- it runs K9a instead (csrc/kernels/gemm_w8a8.hip):
+# kgc.act_quant_fp8 quantises the activation rows to e4m3 with one fp32 scale per row
+# (quant.quantize_fp8_rows, bit for bit) and kgc.w8a8_gemm multiplies them with the e4m3
+# weight, read in place, on the fp8 MFMA, the two scales meeting the fp32 sums in the
+# epilogue.  The tile configuration is a fixed rule of (M, N) (``W8A8Method.a8_cfg``: all
+# configurations return the same bits, so nothing is timed).  Shapes K9a refuses (N or K not
+# a multiple of 128, K > 16384, an x it cannot read) and KGC_W8A8_GEMM=0 keep the widen path,
+# whose scratch stays reserved for them.  The CPU path applies the same rule with the same
+# arithmetic, so a CPU engine is the oracle of a GPU one.
 _U8 = torch.uint8               # a --quantization mxfp4 weight's codes
 _q_scratch: dict[tuple, torch.Tensor] = {}
 _q_scratch_old: list = []       # outgrown scratches stay alive: captured graphs write them
@@ -304,6 +318,11 @@ class QuantMethod:
             out = torch.empty(M, N, dtype=x.dtype, device=x.device)
             _kgc().splitk_reduce(out, self.dgemm(x, w, cfg, S))
             return out
+        return self.rest_linear(x, w, scale, bias)
+
+    def rest_linear(self, x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor,
+                    bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """What ``linear`` runs where neither K9q / K9f nor the mid-M plan serves the call."""
         return self.widen_linear(x, w, scale, bias)
 
     def linear_silu(self, x: torch.Tensor, w: torch.Tensor,
@@ -548,7 +567,96 @@ W4 = QuantMethod(
     op_mid=lambda out, x, w4, e, bias, cfg, epi: _kgc().w4_dgemm(out, x, e[1], bias, cfg, epi),
     op_pack=_w4_op_pack,
     op_tiles=lambda: [_kgc().w4_dgemm_cfg_info(c) for c in range(int(_kgc().w4_dgemm_num_cfgs()))])
-QUANT_METHODS = {q.method: q for q in (W8, W4)}
+
+
+A8_MAX_K = 16384                # act_quant_fp8 keeps a whole activation row in registers
+
+
+@dataclass(eq=False)
+class W8A8Method(QuantMethod):
+    """--quantization fp8_w8a8: W8's fields and methods; ``rest_linear`` runs K9a
+    (act_quant_fp8 + w8a8_gemm) where it fits, and the CPU path mirrors that rule."""
+
+    def __post_init__(self):
+        super().__post_init__()
+        # KGC_W8A8_GEMM=0: K9a off, the widen path as under --quantization fp8
+        self.a8_enabled = os.environ.get("KGC_W8A8_GEMM", "1") != "0"
+        self.counts["k9a"] = 0
+        self._a8_tiles: list = []   # (BM, BN, ring slots) per K9a configuration id
+
+    def a8_tiles(self) -> list:
+        if not self._a8_tiles:
+            k = _kgc()
+            self._a8_tiles.extend(tuple(int(v) for v in k.w8a8_gemm_cfg_info(c))
+                                  for c in range(int(k.w8a8_gemm_num_cfgs())))
+        return self._a8_tiles
+
+    def a8_fits(self, M: int, N: int, K: int) -> bool:
+        """The rule both devices share: more rows than K9q takes, whole 128-wide tiles."""
+        return M > SKINNY_MAX_M and N % 128 == 0 and K % 128 == 0
+
+    def a8_cfg(self, M: int, N: int) -> int:
+        """K9a's configuration, a fixed rule of (M, N) (every configuration returns the same
+        bits), read off profiles/w8a8_gemm_vs_widen.jsonl (Llama-3-8B projections, M = 128 ..
+        16384): 128 x 128 tiles up to 128 rows and wherever 256 x 128 tiles would leave CUs
+        without a workgroup (M = 512 at N <= 6144: 34-99 us against 43-123 us); 256 x 256
+        tiles where N has no half tile and their workgroups fill at least 90 % of whole
+        rounds of the 256 CUs (N = 4096 at M >= 8192: 175 / 512 us against 191 / 596 us); 256 x
+        128 otherwise (gate_up at M = 2048: 296 us against 330 us on 3.5 rounds of 256 x 256)."""
+        mb, cus = -(-M // 256), 256
+        big = mb * (N // 256)
+        if M <= 128 or mb * (N // 128) < cus:
+            want = (128, 128)
+        elif N % 256 == 0 and big >= cus and big >= 0.9 * cus * -(-big // cus):
+            want = (256, 256)
+        else:
+            want = (256, 128)
+        return next(c for c, t in enumerate(self.a8_tiles()) if t[:2] == want)
+
+    def a8_gemm(self, x: torch.Tensor, w: torch.Tensor, scale: torch.Tensor,
+                bias: Optional[torch.Tensor] = None, cfg: Optional[int] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """K9a: quantise x's rows to e4m3, then (xq w8^T) * xs[m] * scale[n] (+ bias)."""
+        k = _kgc()
+        M, K = x.shape
+        N = w.shape[0]
+        xq = torch.empty(M, K, dtype=_FP8, device=x.device)
+        xs = torch.empty(M, dtype=torch.float32, device=x.device)
+        k.act_quant_fp8(xq, xs, x)
+        if out is None:
+            out = torch.empty(M, N, dtype=x.dtype, device=x.device)
+        k.w8a8_gemm(out, xq, xs, w, scale, bias, self.a8_cfg(M, N) if cfg is None else cfg)
+        self.counts["k9a"] += 1
+        return out
+
+    def rest_linear(self, x, w, scale, bias=None):
+        N, K = self.nk(w)
+        if (self.a8_enabled and takes_act_fp8(w) and self.a8_fits(x.shape[0], N, K)
+                and K <= A8_MAX_K and _q_x_ok(x) and w.is_contiguous()
+                and (bias is None or (bias.is_contiguous() and bias.dtype == x.dtype))):
+            return self.a8_gemm(x, w, scale, bias)
+        return self.widen_linear(x, w, scale, bias)
+
+    def linear(self, x, w, bias=None):
+        if not x.is_cuda and takes_act_fp8(w):
+            N, K = self.nk(w)
+            x2 = x.reshape(-1, K)
+            if self.a8_fits(x2.shape[0], N, K):
+                xq, xs = quantize_fp8_rows(x2)
+                y = F.linear(dequantize_fp8_rows(xq, xs, x.dtype),
+                             self.dequant(w, self.scale(w), x.dtype), bias)
+                return y.view(*x.shape[:-1], N)
+        return super().linear(x, w, bias)
+
+
+W8A8 = W8A8Method(**{**{f: getattr(W8, f) for f in W8.__dataclass_fields__},
+                     "method": "fp8_w8a8"})
+QUANT_METHODS = {q.method: q for q in (W8, W4, W8A8)}
+
+
+def _fp8_method(w: torch.Tensor) -> QuantMethod:
+    """The method of an e4m3 weight: W8A8 if it is marked as taking fp8 activations."""
+    return W8A8 if takes_act_fp8(w) else W8
 
 # the names callers use, bound to the shared implementation; the plan dicts are the
 # instances' own objects (tests write into them, ``clear_plan`` clears them in place)
@@ -763,7 +871,7 @@ def linear_silu(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
     reduction (``splitk_reduce_silu``), so the [M, 2I] gate_up output never exists."""
     from . import _k, silu_mul
     if w.dtype == _FP8:
-        return w8_linear_silu(x, w, bias)
+        return _fp8_method(w).linear_silu(x, w, bias)
     if w.dtype == _U8:
         return w4_linear_silu(x, w, bias)
     if bias is None and x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and _plan_silu:
@@ -788,7 +896,7 @@ def linear_qkv(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     runs K9m split-K at this (M, N, K) -- its fp32 K-slices [S, M, N], which that kernel
     sums (``ops.rope_kv_write``), so the reduction needs no launch of its own."""
     if w.dtype == _FP8:
-        return w8_linear(x, w)
+        return _fp8_method(w).linear(x, w)
     if w.dtype == _U8:
         return w4_linear(x, w)
     p = _dg_plan(x, w, "qkv")
@@ -806,7 +914,7 @@ def linear_add_rms(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor,
     one kernel (``splitk_add_rms_norm``); otherwise the GEMM and ``fused_add_rms_norm``."""
     from . import _k, fused_add_rms_norm
     if w.dtype == _FP8:
-        return W8.linear_add_rms(x, w, residual, gamma, eps)
+        return _fp8_method(w).linear_add_rms(x, w, residual, gamma, eps)
     if w.dtype == _U8:
         return W4.linear_add_rms(x, w, residual, gamma, eps)
     if _plan_accnorm and x.is_cuda and x.dim() == 2 and x.stride(1) == 1:
@@ -844,7 +952,7 @@ def skinny_gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], 
 
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     if w.dtype == _FP8:
-        return w8_linear(x, w, bias)
+        return _fp8_method(w).linear(x, w, bias)
     if w.dtype == _U8:
         return w4_linear(x, w, bias)
     if x.is_cuda and x.dim() == 2 and x.shape[0] <= SKINNY_MAX_M and _plan:
@@ -1095,7 +1203,7 @@ def save_dg_table(path: str, res: dict, meta: dict) -> int:
 
 
 def clear_plan() -> None:
-    for q in (W8, W4):
+    for q in QUANT_METHODS.values():
         q.plan_dg.clear()
         q.plan.clear()
         q.plan_silu.clear()

@@ -1,5 +1,9 @@
 """Weight-only quantisation of linear weights: ``--quantization fp8`` (W8A16, below) and
 ``--quantization mxfp4`` (W4A16, OCP MXFP4: the second half of this file).
+``--quantization fp8_w8a8`` makes the same e4m3 weights as ``fp8`` and marks each as taking
+fp8 activations (``mark_act_fp8``): where the W8A16 kernels do not serve a call, the
+activation rows are quantised online with the same ``quantize_fp8_rows`` and the product
+runs on the fp8 MFMA (ops/gemm.py W8A8, csrc/kernels/gemm_w8a8.hip).
 
 A weight [N, K] becomes OCP e4m3 (``torch.float8_e4m3fn``) with one fp32 scale per output
 row: ``scale = amax(|row|) / 448``, so each row uses the whole e4m3 range, and
@@ -16,7 +20,7 @@ import torch
 
 FP8 = torch.float8_e4m3fn
 FP8_MAX = 448.0
-QUANTIZATION_METHODS = ("fp8", "mxfp4")
+QUANTIZATION_METHODS = ("fp8", "mxfp4", "fp8_w8a8")
 
 
 def quantize_fp8_rows(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
@@ -39,6 +43,18 @@ def attach_scale(w8: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
 
 def is_fp8(w: torch.Tensor) -> bool:
     return w.dtype == FP8
+
+
+def mark_act_fp8(w8: torch.Tensor) -> torch.Tensor:
+    """Mark an fp8 weight as one of a ``--quantization fp8_w8a8`` model.  Like the scale, the
+    mark is an attribute of the tensor object: set it on the ``nn.Parameter`` that wraps it."""
+    assert w8.dtype == FP8
+    w8.w8_act = True  # type: ignore[attr-defined]
+    return w8
+
+
+def takes_act_fp8(w: torch.Tensor) -> bool:
+    return w.dtype == FP8 and getattr(w, "w8_act", False)
 
 
 def w8_scale(w8: torch.Tensor) -> torch.Tensor:

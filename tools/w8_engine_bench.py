@@ -12,7 +12,9 @@ ones, and each line then carries the W8 plan of its bucket (``w8_plan``: shape a
 [cfg, S], or "widen").  With ``--quantization mxfp4`` a line of a batch <= 64 carries the W4
 plan of its bucket (``w4_plan``: shape -> K9f [mt, nt, nw], or "widen"); a larger batch the
 K9mf plan of its bucket (``w4_dg_plan``: shape and kind -> [cfg, S], or "widen").  ``--tag``
-labels the lines, ``--out`` appends them to a file.
+labels the lines, ``--out`` appends them to a file.  ``--prefill N`` times the prefill of N
+prompts of ``--input-len`` tokens instead (one generated token each, the second wave timed):
+wall time, p50 TTFT and prompt tok/s, with any ``--quantization`` value, fp8_w8a8 included.
 """
 import argparse
 import json
@@ -34,6 +36,8 @@ def main():
     ap.add_argument("--output-len", type=int, default=128)
     ap.add_argument("--tag", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--prefill", type=int, default=0, metavar="N",
+                    help="time the prefill of N prompts of --input-len tokens instead of decode")
     ap.add_argument("--blocks-only", action="store_true",
                     help="report the KV block count and stop (no graphs, no decode)")
     a = ap.parse_args()
@@ -61,6 +65,27 @@ def main():
         emit(base)
         return
     from kubernetes_gpu_cluster_amd.ops import gemm
+    if a.prefill:
+        # the bench workload's prefill: N prompts of --input-len tokens, one output token
+        # each; the second wave is timed (the first warms up)
+        g = torch.Generator().manual_seed(0)
+        for rep in range(2):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            seqs = [eng.add_request(torch.randint(100, 100000, (a.input_len,), generator=g).tolist(),
+                                    SamplingParams(temperature=0.0, max_tokens=1, ignore_eos=True))
+                    for _ in range(a.prefill)]
+            while eng.has_unfinished():
+                eng.step()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            ttft = sorted(s.first_token_time - s.arrival_time for s in seqs)
+        emit(dict(base, prompts=a.prefill, input_len=a.input_len,
+                  prefill_s=round(t1 - t0, 4), p50_ttft_ms=round(ttft[len(ttft) // 2] * 1e3, 1),
+                  prefill_tok_s=round(a.prefill * a.input_len / (t1 - t0)),
+                  quant_counts={m: dict(q.counts) for m, q in gemm.QUANT_METHODS.items()
+                                if any(q.counts.values())}))
+        return
     w8_plan = getattr(gemm, "w8_dg_plan", dict)()
     g = torch.Generator().manual_seed(0)
     for B in batches:
