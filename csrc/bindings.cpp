@@ -603,6 +603,54 @@ void moe_gate_route(Tensor topk_w, Tensor topk_ids, Tensor x, Tensor wg, bool re
                              topk_ids.data_ptr<int>(), stream());
 }
 
+// K13w: the two routers for wide expert counts (moe_route_wide.hip)
+static void check_route_out(const Tensor& ref, const Tensor& topk_w, const Tensor& topk_ids,
+                            int64_t T, int64_t k) {
+  TORCH_CHECK(topk_w.scalar_type() == at::kFloat && topk_w.is_contiguous() && topk_w.numel() == T * k,
+              "topk_w fp32 [T, k]");
+  TORCH_CHECK(topk_ids.scalar_type() == at::kInt && topk_ids.is_contiguous() &&
+              topk_ids.numel() == T * k, "topk_ids int32 [T, k]");
+  check_same_dev(ref, topk_w, "topk_w");
+  check_same_dev(ref, topk_ids, "topk_ids");
+}
+
+void moe_route_wide(Tensor topk_w, Tensor topk_ids, Tensor logits, bool renorm) {
+  check_gpu(logits, "logits");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(logits.device());
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1 && topk_w.dim() == 2,
+              "router logits [T, E] dense rows, topk_w [T, k]");
+  const int64_t T = logits.size(0), E = logits.size(1), k = topk_w.size(-1);
+  TORCH_CHECK(E > 64 && E <= 256 && k >= 1 && k <= 16, "64 < E <= 256, 1 <= k <= 16");
+  TORCH_CHECK(T < INT32_MAX && (T <= 1 || logits.stride(0) >= E), "rows must not overlap");
+  check_route_out(logits, topk_w, topk_ids, T, k);
+  if (T == 0) return;
+  kgc::launch_moe_route_wide(dt_code(logits), logits.data_ptr(), logits.stride(0), (int)T, (int)E,
+                             (int)k, renorm, topk_w.data_ptr<float>(), topk_ids.data_ptr<int>(),
+                             stream());
+}
+
+void moe_gate_route_wide(Tensor topk_w, Tensor topk_ids, Tensor x, Tensor wg, bool renorm) {
+  check_gpu(x, "x");
+  c10::hip::HIPGuardMasqueradingAsCUDA g(x.device());
+  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0 && topk_w.dim() == 2 &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "x [T, H], 16-B aligned rows; topk_w [T, k]");
+  TORCH_CHECK(wg.dim() == 2 && wg.is_contiguous() && wg.scalar_type() == x.scalar_type() &&
+                  (x.scalar_type() == at::kBFloat16 || x.scalar_type() == at::kHalf) &&
+                  reinterpret_cast<uintptr_t>(wg.data_ptr()) % 16 == 0,
+              "wg [E, H] contiguous, 16-B aligned, x's dtype (bf16 / fp16)");
+  const int64_t T = x.size(0), H = x.size(1), E = wg.size(0), k = topk_w.size(-1);
+  TORCH_CHECK(wg.size(1) == H && H >= 256 && H % 256 == 0 && H <= (1 << 20), "H % 256 == 0");
+  TORCH_CHECK(E > 16 && E <= 256 && k >= 1 && k <= 16, "16 < E <= 256, 1 <= k <= 16");
+  TORCH_CHECK(T < INT32_MAX - 16 && (T <= 1 || x.stride(0) >= H), "rows must not overlap");
+  check_route_out(x, topk_w, topk_ids, T, k);
+  check_same_dev(x, wg, "moe_gate_route_wide");
+  if (T == 0) return;
+  kgc::launch_moe_gate_route_wide(dt_code(x), x.data_ptr(), x.stride(0), wg.data_ptr(), (int)H,
+                                  (int)E, (int)T, (int)k, renorm, topk_w.data_ptr<float>(),
+                                  topk_ids.data_ptr<int>(), stream());
+}
+
 void moe_align(Tensor sorted_ids, Tensor block_expert, Tensor meta, Tensor topk_ids, int64_t e0,
                int64_t E_local, int64_t bm) {
   check_gpu(topk_ids, "topk_ids");
@@ -1802,6 +1850,9 @@ TORCH_LIBRARY(kgc, m) {
   m.def("moe_route(Tensor(a!) topk_w, Tensor(b!) topk_ids, Tensor logits, bool renorm) -> ()");
   m.def("moe_gate_route(Tensor(a!) topk_w, Tensor(b!) topk_ids, Tensor x, Tensor wg, "
         "bool renorm) -> ()");
+  m.def("moe_route_wide(Tensor(a!) topk_w, Tensor(b!) topk_ids, Tensor logits, bool renorm) -> ()");
+  m.def("moe_gate_route_wide(Tensor(a!) topk_w, Tensor(b!) topk_ids, Tensor x, Tensor wg, "
+        "bool renorm) -> ()");
   m.def("moe_align(Tensor(a!) sorted_ids, Tensor(b!) block_expert, Tensor(c!) meta, "
         "Tensor topk_ids, int e0, int E_local, int bm) -> ()");
   m.def("moe_gemm(Tensor(a!) C, Tensor A, Tensor W, Tensor sorted_ids, Tensor block_expert, "
@@ -1924,6 +1975,8 @@ TORCH_LIBRARY_IMPL(kgc, CUDA, m) {
   m.impl("ep_combine", &ep_combine);
   m.impl("moe_route", &moe_route);
   m.impl("moe_gate_route", &moe_gate_route);
+  m.impl("moe_route_wide", &moe_route_wide);
+  m.impl("moe_gate_route_wide", &moe_gate_route_wide);
   m.impl("moe_align", &moe_align);
   m.impl("moe_gemm", &moe_gemm);
   m.impl("moe_dgemm", &moe_dgemm);

@@ -42,7 +42,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # per-file flags.  New kernels are compiled without the packed fp32 instructions
 # (v_pk_add / mul / fma_f32); the older files keep the flags their numbers were taken with.
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"logits_process.hip": NO_PK_F32, "gemm_w8a8.hip": NO_PK_F32}
+EXTRA_FLAGS = {"logits_process.hip": NO_PK_F32, "gemm_w8a8.hip": NO_PK_F32,
+               "moe_route_wide.hip": NO_PK_F32}
 
 
 def _torch_paths():

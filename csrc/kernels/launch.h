@@ -196,6 +196,13 @@ void launch_moe_route(int dtype, const void* logits, int64_t stride, int ntok, i
 void launch_moe_gate_route(int dtype, const void* x, int64_t ldx, const void* wg, int H, int E,
                            int ntok, int k, bool renorm, float* topk_w, int* topk_ids,
                            hipStream_t s);
+// K13w (moe_route_wide.hip): the same two for wide expert counts.  Route: 64 < E <= 256,
+// k <= 16.  Gate + route on MFMA: 16 < E <= 256, k <= 16, H % 256 == 0, 16-B aligned rows.
+void launch_moe_route_wide(int dtype, const void* logits, int64_t stride, int ntok, int E, int k,
+                           bool renorm, float* topk_w, int* topk_ids, hipStream_t s);
+void launch_moe_gate_route_wide(int dtype, const void* x, int64_t ldx, const void* wg, int H,
+                                int E, int ntok, int k, bool renorm, float* topk_w,
+                                int* topk_ids, hipStream_t s);
 void launch_moe_align(const int* topk_ids, int npairs, int e0, int E_local, int bm, int max_rows,
                       int* sorted_ids, int* block_expert, int* meta, hipStream_t s);
 // splitk > 1 (scatter only): C is S fp32 slices of slice_stride elements each

@@ -96,12 +96,15 @@ def full_state_dict_random(cfg: ModelConfig, seed: int = 0, std: float = 0.02,
             sd[p + "self_attn.q_norm.weight"] = 1 + rnd(d)
             sd[p + "self_attn.k_norm.weight"] = 1 + rnd(d)
         if cfg.is_moe:
-            q = p + "block_sparse_moe."
+            # Mixtral's names, or (arch qwen3) the per-expert hub names of Qwen3-MoE
+            qw = cfg.arch == "qwen3"
+            q = p + ("mlp." if qw else "block_sparse_moe.")
+            w1, w3, w2 = ("gate_proj", "up_proj", "down_proj") if qw else ("w1", "w3", "w2")
             sd[q + "gate.weight"] = rnd(cfg.num_experts, H) * 10
             for e in range(cfg.num_experts):
-                sd[q + f"experts.{e}.w1.weight"] = rnd(I, H)
-                sd[q + f"experts.{e}.w3.weight"] = rnd(I, H)
-                sd[q + f"experts.{e}.w2.weight"] = rnd(H, I)
+                sd[q + f"experts.{e}.{w1}.weight"] = rnd(I, H)
+                sd[q + f"experts.{e}.{w3}.weight"] = rnd(I, H)
+                sd[q + f"experts.{e}.{w2}.weight"] = rnd(H, I)
         else:
             sd[p + "mlp.gate_proj.weight"] = rnd(I, H)
             sd[p + "mlp.up_proj.weight"] = rnd(I, H)

@@ -46,6 +46,7 @@ class ModelConfig:
     # MoE
     num_experts: int = 0
     top_k_experts: int = 0
+    norm_topk_prob: bool = True  # renormalise the top-k router weights (Qwen3-MoE's flag)
     bos_token_id: int = 1
     eos_token_id: int = 2
 
@@ -114,6 +115,11 @@ PRESETS: dict[str, ModelConfig] = {
     "qwen3-14b": ModelConfig("qwen3-14b", "qwen3", 40, 5120, 40, 8, 128, 17408, 151936,
                              max_position=40960, rope_theta=1e6, rms_eps=1e-6,
                              qk_norm=True, bos_token_id=151643, eos_token_id=151645),
+    # Qwen3-MoE: Qwen3 attention, every layer sparse (128 experts, top-8; K13w routes them)
+    "qwen3-30b-a3b": ModelConfig("qwen3-30b-a3b", "qwen3", 48, 2048, 32, 4, 128, 768, 151936,
+                                 max_position=40960, rope_theta=1e6, rms_eps=1e-6, qk_norm=True,
+                                 num_experts=128, top_k_experts=8, bos_token_id=151643,
+                                 eos_token_id=151645),
     "qwen2.5-7b": ModelConfig("qwen2.5-7b", "qwen2", 28, 3584, 28, 4, 128, 18944, 152064,
                               max_position=32768, rope_theta=1e6, rms_eps=1e-6, qkv_bias=True,
                               bos_token_id=151643, eos_token_id=151643),
@@ -145,6 +151,9 @@ PRESETS: dict[str, ModelConfig] = {
     "tiny-mixtral": ModelConfig("tiny-mixtral", "mixtral", 2, 256, 4, 2, 64, 384, 1024,
                                 max_position=2048, rope_theta=1e6, num_experts=4,
                                 top_k_experts=2),
+    "tiny-qwen3-moe": ModelConfig("tiny-qwen3-moe", "qwen3", 2, 256, 4, 2, 64, 128, 1024,
+                                  max_position=2048, rope_theta=1e6, rms_eps=1e-6, qk_norm=True,
+                                  num_experts=128, top_k_experts=8),
 }
 
 # HF repo basenames (lower-cased) -> preset
@@ -155,11 +164,14 @@ _ALIASES = {
     "meta-llama-3-70b": "llama-3-70b", "meta-llama-3-70b-instruct": "llama-3-70b",
     "mixtral-8x7b-v0.1": "mixtral-8x7b", "mixtral-8x7b-instruct-v0.1": "mixtral-8x7b",
     "qwen2.5-7b-instruct": "qwen2.5-7b", "qwen3-0.6b-base": "qwen3-0.6b",
+    "qwen3-30b-a3b-base": "qwen3-30b-a3b", "qwen3-30b-a3b-instruct-2507": "qwen3-30b-a3b",
+    "qwen3-30b-a3b-thinking-2507": "qwen3-30b-a3b",
 }
 
 
-def _from_hf_config(d: dict, name: str) -> ModelConfig:
-    """Map an HF config.json dict onto ModelConfig."""
+def config_from_hf(d: dict, name: str) -> ModelConfig:
+    """Map an HF config.json dict onto ModelConfig (``model_type: qwen3_moe`` -> arch
+    ``qwen3`` with the expert fields; a key it omits takes the hub class's default)."""
     mt = d.get("model_type", "llama")
     if mt == "opt":
         h = d["hidden_size"]
@@ -182,18 +194,29 @@ def _from_hf_config(d: dict, name: str) -> ModelConfig:
     nh = d["num_attention_heads"]
     h = d["hidden_size"]
     arch = {"llama": "llama", "qwen2": "qwen2", "qwen3": "qwen3", "mistral": "llama",
-            "mixtral": "mixtral"}.get(mt, "llama")
+            "mixtral": "mixtral", "qwen3_moe": "qwen3"}.get(mt, "llama")
     eos = d.get("eos_token_id", 2)
     if isinstance(eos, list):
         eos = eos[0]
+    inter, experts = d["intermediate_size"], d.get("num_local_experts", 0)
+    if mt == "qwen3_moe":
+        # every layer sparse: a stack mixing dense and MoE MLPs is not built here
+        if d.get("mlp_only_layers"):
+            raise ValueError(f"{name}: mlp_only_layers = {d['mlp_only_layers']} (dense layers "
+                             f"inside a qwen3_moe stack) is not supported")
+        if d.get("decoder_sparse_step", 1) != 1:
+            raise ValueError(f"{name}: decoder_sparse_step = {d['decoder_sparse_step']} is not "
+                             f"supported (only 1: every layer is a MoE layer)")
+        inter, experts = d["moe_intermediate_size"], d["num_experts"]
     return ModelConfig(
         name, arch, d["num_hidden_layers"], h, nh, d.get("num_key_value_heads", nh),
-        d.get("head_dim") or h // nh, d["intermediate_size"], d["vocab_size"],
+        d.get("head_dim") or h // nh, inter, d["vocab_size"],
         max_position=d.get("max_position_embeddings", 8192),
         rope_theta=float(d.get("rope_theta", 10000.0)), rope_scaling=d.get("rope_scaling"),
         rms_eps=d.get("rms_norm_eps", 1e-6), tie_embeddings=d.get("tie_word_embeddings", False),
         qkv_bias=(arch == "qwen2") or d.get("attention_bias", False), qk_norm=(arch == "qwen3"),
-        num_experts=d.get("num_local_experts", 0), top_k_experts=d.get("num_experts_per_tok", 0),
+        num_experts=experts, top_k_experts=d.get("num_experts_per_tok", 0),
+        norm_topk_prob=bool(d.get("norm_topk_prob", False)) if mt == "qwen3_moe" else True,
         bos_token_id=d.get("bos_token_id", 1) or 1, eos_token_id=eos)
 
 
@@ -204,7 +227,7 @@ def resolve_model(model: str) -> tuple[ModelConfig, Optional[str]]:
         return PRESETS[key], None
     if os.path.isdir(model) and os.path.isfile(os.path.join(model, "config.json")):
         with open(os.path.join(model, "config.json")) as f:
-            cfg = _from_hf_config(json.load(f), os.path.basename(model.rstrip("/")))
+            cfg = config_from_hf(json.load(f), os.path.basename(model.rstrip("/")))
         return cfg, model
     base = os.path.basename(key)
     base = _ALIASES.get(base, base)

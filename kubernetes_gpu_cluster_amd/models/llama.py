@@ -1,5 +1,5 @@
 """Llama-family decoder: Llama-3 (8B/70B), Mistral, Qwen2/2.5, Qwen3 (q/k norm),
-Qwen v1 (fused c_attn, ``--trust-remote-code`` arch) and Mixtral (MoE).
+Qwen v1 (fused c_attn, ``--trust-remote-code`` arch), Mixtral and Qwen3-MoE (MoE).
 
 Per layer:
   fused_add_rms_norm (K4) -> QKV GEMM -> rope_kv_write (K3/K5/K6) -> paged attention

@@ -1,4 +1,5 @@
-"""Mixtral sparse-MoE block (K13 top-k softmax routing, K14 grouped expert MLP).
+"""Sparse-MoE block of Mixtral (8 experts, top-2) and Qwen3-MoE (128 experts, top-8): K13 /
+K13w top-k softmax routing, K14 grouped expert MLP.
 
 Expert placement over the TP group (``--moe-parallel``):
 
@@ -170,7 +171,9 @@ class MoEBlock(nn.Module):
     def map_weight(self, rest: str):
         """Checkpoint names under ``block_sparse_moe.``: gate.weight,
         experts.{e}.w{1,2,3}.weight; or the fused transformers-v5 names under ``mlp.``:
-        gate.weight, experts.gate_up_proj [E, 2I, H], experts.down_proj [E, H, I]."""
+        gate.weight, experts.gate_up_proj [E, 2I, H], experts.down_proj [E, H, I]; or the
+        per-expert hub names of Qwen3-MoE under ``mlp.``:
+        experts.{e}.{gate_proj,up_proj,down_proj}.weight (= w1, w3, w2)."""
         if rest.startswith("gate."):
             return self.gate.weight, None
         if rest in ("experts.gate_up_proj", "experts.down_proj"):
@@ -188,6 +191,7 @@ class MoEBlock(nn.Module):
             return ("moe", load_fused), None
         parts = rest.split(".")
         e, which = int(parts[1]), parts[2]
+        which = {"gate_proj": "w1", "up_proj": "w3", "down_proj": "w2"}.get(which, which)
         le = e - self.e0
         if not (0 <= le < self.E_local):
             return None
@@ -207,10 +211,11 @@ class MoEBlock(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         # decode sizes: the router GEMM inside the top-k kernel (ops.moe_gate_topk); prefill
         # chunks keep the GEMM (whose 16K-row output a single wave per token would serialise)
-        r = (ops.moe_gate_topk(x, self.gate.weight, self.k)
+        renorm = self.cfg.norm_topk_prob
+        r = (ops.moe_gate_topk(x, self.gate.weight, self.k, renorm)
              if x.shape[0] <= ops.MOE_GATE_FUSED_MAX_T and self.gate.bias is None else None)
         if r is None:
-            r = ops.moe_topk_softmax(self.gate(x), self.k)
+            r = ops.moe_topk_softmax(self.gate(x), self.k, renorm)
         topk_w, topk_ids = r
         if self.mode == "tp":
             return comm.tp_all_reduce(self.experts(x, topk_w, topk_ids))

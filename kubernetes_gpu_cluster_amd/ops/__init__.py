@@ -595,13 +595,17 @@ def moe_supported(n: int, k: int) -> bool:
 
 
 def moe_topk_softmax(router_logits: torch.Tensor, k: int, renormalize: bool = True):
-    """K13: (weights fp32 [T, k], expert ids int32 [T, k])."""
+    """K13 (E <= 64) / K13w (64 < E <= 256, k <= 16): (weights fp32 [T, k], expert ids
+    int32 [T, k])."""
     if not _gpu(router_logits):
         return ref.moe_topk_softmax(router_logits, k, renormalize)
-    T = router_logits.shape[0]
+    T, E = router_logits.shape
     w = torch.empty(T, k, dtype=torch.float32, device=router_logits.device)
     ids = torch.empty(T, k, dtype=torch.int32, device=router_logits.device)
-    _k().moe_route(w, ids, router_logits, renormalize)
+    if E > 64:
+        _k().moe_route_wide(w, ids, router_logits, renormalize)
+    else:
+        _k().moe_route(w, ids, router_logits, renormalize)
     return w, ids
 
 
@@ -609,15 +613,23 @@ def moe_gate_topk(x: torch.Tensor, wg: torch.Tensor, k: int,
                   renormalize: bool = True) -> Optional[tuple]:
     """K13 with the router GEMM folded in: (weights fp32 [T, k], expert ids int32 [T, k])
     of x [T, H] . wg [E, H]^T in one launch, or None where the fused kernel does not apply
-    (CPU, E > 16, H % 512 != 0): the caller then runs the GEMM and ``moe_topk_softmax``."""
-    if (not _gpu(x) or x.dim() != 2 or wg.shape[0] > 16 or x.shape[1] % 512
+    (CPU, E > 256, H % 512 != 0 at E <= 16, H % 256 != 0 or k > 16 above, rows not 16-byte
+    aligned): the caller then runs the GEMM and ``moe_topk_softmax``.  E <= 16 keeps every
+    expert's dot product in registers (K13); 16 < E <= 256 runs the GEMM on MFMA (K13w)."""
+    E = wg.shape[0]
+    wide = E > 16
+    if (not _gpu(x) or x.dim() != 2 or E > 256 or x.shape[1] % (256 if wide else 512)
             or x.dtype not in (torch.bfloat16, torch.float16) or wg.dtype != x.dtype
-            or x.stride(1) != 1 or x.stride(0) % 8):
+            or x.stride(1) != 1 or x.stride(0) % 8
+            or (wide and (k > 16 or x.shape[1] == 0 or x.data_ptr() % 16))):
         return None
     T = x.shape[0]
     w = torch.empty(T, k, dtype=torch.float32, device=x.device)
     ids = torch.empty(T, k, dtype=torch.int32, device=x.device)
-    _k().moe_gate_route(w, ids, x, wg.contiguous(), renormalize)
+    if wide:
+        _k().moe_gate_route_wide(w, ids, x, wg.contiguous(), renormalize)
+    else:
+        _k().moe_gate_route(w, ids, x, wg.contiguous(), renormalize)
     return w, ids
 
 

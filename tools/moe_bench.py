@@ -1,6 +1,10 @@
 """Grouped-GEMM MoE block vs the per-expert hipBLASLt loop, Mixtral-8x7B shapes.
 
     python tools/moe_bench.py [--tokens 256 1024 8192]
+
+Router mode (K13w, Qwen3-MoE shapes: E = 128, top-8, H = 2048):
+
+    python tools/moe_bench.py --router [--tokens 1 64 256 1024] [--out profiles/moe_route_wide.jsonl]
 """
 import argparse
 import json
@@ -23,7 +27,52 @@ def timeit(fn, iters=10):
     return (time.perf_counter() - t) / iters
 
 
+def router(a):
+    """K13w fused (router GEMM on MFMA inside the top-k kernel) vs hipBLASLt GEMM +
+    moe_route_wide vs the torch formulation, alternating in one process; one JSON line per
+    T, appended to --out.  Times are host clocks around `iters` calls ending in a device
+    synchronise (launch overhead included, as the eager engine pays it)."""
+    import torch.nn.functional as F
+    from kubernetes_gpu_cluster_amd import ops
+    dev, dt = torch.device("cuda"), torch.bfloat16
+    wg = (torch.randn(a.E, a.H, device=dev) / a.H ** 0.5).to(dt)
+
+    def torch_route(x):
+        w, ids = torch.topk(torch.softmax(F.linear(x, wg).float(), -1), a.k, -1)
+        return w / w.sum(-1, keepdim=True), ids
+
+    for T in a.tokens:
+        x = (torch.randn(T, a.H, device=dev) * 0.5).to(dt)
+        fns = {"fused_us": lambda: ops.moe_gate_topk(x, wg, a.k),
+               "gemm_route_us": lambda: ops.moe_topk_softmax(F.linear(x, wg), a.k),
+               "torch_us": lambda: torch_route(x)}
+        assert fns["fused_us"]() is not None, "fused router kernel does not take this shape"
+        same = (fns["fused_us"]()[1].sort(1).values == fns["gemm_route_us"]()[1].sort(1).values)
+        best = {n: float("inf") for n in fns}
+        for _ in range(a.rounds):                      # alternate; keep each one's best round
+            for n, fn in fns.items():
+                best[n] = min(best[n], timeit(fn, a.iters))
+        row = {"mode": "router", "E": a.E, "k": a.k, "H": a.H, "dtype": "bf16", "T": T,
+               "rows_same_experts": round(same.all(1).float().mean().item(), 4),
+               **{n: round(t * 1e6, 2) for n, t in best.items()}}
+        print(json.dumps(row), flush=True)
+        if a.out:
+            with open(a.out, "a") as f:
+                f.write(json.dumps(row) + "\n")
+
+
 def main():
+    if "--router" in sys.argv:
+        ap = argparse.ArgumentParser()
+        ap.add_argument("--router", action="store_true")
+        ap.add_argument("--tokens", type=int, nargs="+", default=[1, 64, 256, 1024])
+        ap.add_argument("--H", type=int, default=2048)
+        ap.add_argument("--E", type=int, default=128)
+        ap.add_argument("--k", type=int, default=8)
+        ap.add_argument("--iters", type=int, default=5000)
+        ap.add_argument("--rounds", type=int, default=5)
+        ap.add_argument("--out", default="")
+        return router(ap.parse_args())
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", type=int, nargs="+", default=[64, 256, 1024, 8192])
     ap.add_argument("--H", type=int, default=4096)
